@@ -20,6 +20,10 @@ product, fp32 accumulate; include/mispec.h MISPEC_PREC_F16X3; ~1e-7 of the spect
 (split bf16, ~5e-6 of the peak) and "fp32" (fp32 MFMA), each with the dynamic range measured on this
 device and its matrix-pipe roofline.
 
+``--dump-outputs DIR`` writes what the last timed step returned (rank 0) to DIR/<workload>.npy after the timed
+steps, at most 64 MB (a fixed seeded sample of a larger output, with its positions in DIR/<workload>_index.npy).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 ``python bench.py --gpus N`` without a torch.distributed environment starts its own N ranks
 (``python -m torch.distributed.run``, one per GPU, RCCL) and relays rank 0's line.
 
@@ -253,9 +257,11 @@ def prewarm(module, x, ms):
     return (time.perf_counter() - t0) * 1e3
 
 
-def timed_steps(module, x, steps, warmup, sync):
+def timed_steps(module, x, steps, warmup, sync, keep_last=False):
     """W untimed steps, then exactly K timed steps bracketed by sync() on both sides.
-    Returns (wall seconds, device seconds from events on the launch stream)."""
+    Returns (wall seconds, device seconds from events on the launch stream), and with keep_last
+    also what the last timed step returned (None when K = 0)."""
+    y = None
     with torch.no_grad():
         for _ in range(warmup):
             y = module(x)
@@ -269,8 +275,46 @@ def timed_steps(module, x, steps, warmup, sync):
         e1.record()
         sync()
         t1 = time.perf_counter()
+    if keep_last:
+        return t1 - t0, e0.elapsed_time(e1) * 1e-3, (y if steps > 0 else None)
     del y
     return t1 - t0, e0.elapsed_time(e1) * 1e-3
+
+
+DUMP_BUDGET = 60 << 20  # bytes, all arrays of one --dump-outputs together (under 64 MB, headers included)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(y, out_dir, name, budget=DUMP_BUDGET):
+    """Write what a step returned as ``out_dir/<name>.npy`` (float32; float64 stays float64), for comparing two
+    builds output for output.  A tuple / list of tensors becomes ``<name>_<i>``; complex tensors are stored as
+    (..., 2) real pairs.  An array larger than its share of `budget` is replaced by a fixed sample: the elements at
+    sorted flat (C-order) positions drawn with a fixed seed from its shape alone, values in ``<name>.npy`` and
+    the positions (exact in float64) in ``<name>_index.npy``.  Returns {file name: shape written}."""
+    ys = list(y) if isinstance(y, (tuple, list)) else [y]
+    names = [name] if len(ys) == 1 else ["%s_%d" % (name, i) for i in range(len(ys))]
+    share = budget // len(ys) - 4096  # (room for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for nm, t in zip(names, ys):
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        item = t.element_size()
+        n = t.numel()
+        if n * item <= share:
+            arrays = {nm: t.cpu().numpy()}
+        else:
+            # values + float64 positions in the share; drawn with replacement, duplicates dropped
+            k = share // (item + 8)
+            idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, n, size=k))
+            vals = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+            arrays = {nm: vals, nm + "_index": idx.astype(np.float64)}
+        for fn, a in arrays.items():
+            np.save(os.path.join(out_dir, fn + ".npy"), np.ascontiguousarray(a))
+            written[fn + ".npy"] = list(a.shape)
+    return written
 
 
 def module_precision(name, precision):
@@ -831,7 +875,12 @@ def main():
     ap.add_argument("--traffic", default="live", choices=["live", "off"],
                     help="live: rocprofv3 PMC passes over a child process (N=1 only); off: null")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<workload>.npy: "
+                         "float32, at most 64 MB, a fixed seeded sample of a larger output (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     forced = None if args.precision == "auto" else args.precision
 
     if args.pmc_child:
@@ -872,13 +921,17 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return [float(v) for v in t]
 
-    def run_path(mod, xin, me, precision, steps, warmup, fft=True):
+    def run_path(mod, xin, me, precision, steps, warmup, fft=True, keep_last=None):
         """Time `steps` forwards in one arithmetic; whole-job numbers (max over ranks).  precision "fft": the
-        module as it ships (STFT: the FFT path); otherwise the contraction kernels in that arithmetic."""
+        module as it ships (STFT: the FFT path); otherwise the contraction kernels in that arithmetic.
+        keep_last: a list that receives what the last timed step returned."""
         nnaudio_amd.set_precision(None if precision == "fft" else precision)
         old_fft = engine.set_fft(fft)
         try:
-            wall, dev_s = timed_steps(mod, xin, steps, warmup, sync)
+            wall, dev_s, last = timed_steps(mod, xin, steps, warmup, sync, keep_last=True)
+            if keep_last is not None:
+                keep_last.append(last)
+            del last
         finally:
             engine.set_fft(old_fft)
         nnaudio_amd.set_precision(forced)
@@ -938,7 +991,14 @@ def main():
         meta["bound"] = "hbm"
     nnaudio_amd.set_precision(forced)
     prewarm_ms = prewarm(module, x, args.prewarm_ms)
-    wall, dev_s, primary = run_path(module, x, meta, prec, args.steps, args.warmup, fft=use_fft)
+    last = [] if args.dump_outputs else None
+    wall, dev_s, primary = run_path(module, x, meta, prec, args.steps, args.warmup, fft=use_fft, keep_last=last)
+    dumped = None
+    if last is not None:
+        if rank == 0:  # (rank 0's clips are make_input(0): the same as at N = 1)
+            dumped = dump_outputs(last[0], args.dump_outputs, args.workload)
+            log("dump-outputs: %s -> %s" % (dumped, args.dump_outputs))
+        del last
     paths = {prec: primary}
     dominant = None
     if args.workload == "stft":
@@ -1008,6 +1068,9 @@ def main():
                    "time; peak = raw dense MFMA peak of the instruction"),
         "paths": paths,
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                               "what": "the last timed step's output, rank 0; *_index: sampled flat positions"}
     out["roofline"]["dominant_kernel"] = dominant
 
     extra = {}

@@ -137,3 +137,29 @@ def test_reference_operator_sequence_probe_runs_on_the_host_path():
 
     r = bench.reference_ops_on_gpu(torch.randn(2, 6000))
     assert r["unit"] == "frames/s" and r["value"] > 0 and r["max_diff_of_peak"] <= 1e-5, r
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: an output within the budget is written whole (float32); a larger one as a fixed sample
+    whose positions depend on its shape alone, so two runs (two builds) sample the same elements."""
+    import numpy as np
+    import torch
+
+    y = torch.arange(24, dtype=torch.float16).reshape(2, 3, 4)
+    assert bench.dump_outputs(y, str(tmp_path / "a"), "stft") == {"stft.npy": [2, 3, 4]}
+    a = np.load(tmp_path / "a" / "stft.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, y.float().numpy())
+
+    z = torch.randn(64, 100, dtype=torch.float64)
+    budget = 4096 + 2 * 4096 + 1600  # share = budget // 2 - 4096: fits one 800-byte array, samples the other
+    w = bench.dump_outputs((torch.complex(z, -z)[:, :50], z[:1]), str(tmp_path / "b"), "out", budget=budget)
+    assert set(w) == {"out_0.npy", "out_0_index.npy", "out_1.npy"}
+    v, idx = np.load(tmp_path / "b" / "out_0.npy"), np.load(tmp_path / "b" / "out_0_index.npy")
+    assert v.dtype == np.float64 and idx.dtype == np.float64 and v.shape == idx.shape and len(v) > 0
+    full = torch.view_as_real(torch.complex(z, -z)[:, :50]).numpy().reshape(-1)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(v, full[idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b" / "out_1.npy"), z[:1].numpy())
+    sizes = sum(os.path.getsize(tmp_path / "b" / f) for f in w)
+    assert sizes <= budget
+    bench.dump_outputs((torch.complex(z, -z)[:, :50] * 2, z[:1]), str(tmp_path / "c"), "out", budget=budget)
+    assert np.array_equal(np.load(tmp_path / "c" / "out_0_index.npy"), idx)
