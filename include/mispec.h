@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MISPEC_ABI_VERSION 13
+#define MISPEC_ABI_VERSION 14
 
 enum {
   MISPEC_OK = 0,
@@ -681,6 +681,15 @@ int mispec_fir_decimate_host_f32(const float *x, int64_t x_clip_stride, int32_t 
 /* Scratch bytes mispec_fir_decimate_f32 needs (zero-padded clip edges); negative = error. */
 int64_t mispec_fir_decimate_workspace_bytes(int32_t n_clips, int32_t n_samples, int32_t n_taps,
                                             int32_t stride, int32_t pad, int32_t n_out);
+
+/*
+ * Compute units the launch plans are sized for (persistent grids, work split per clip, strip and
+ * fold plans, default octave segments): 1 .. 4096 overrides the device's count for every later
+ * call in the process, 0 restores it.  Returns the previous override (0: none); MISPEC_E_INVALID
+ * for any other value.  Host-only: needs no device.  Results do not depend on it except where a
+ * plan reorders a sum (the strip kernels' passes).
+ */
+int32_t mispec_set_plan_cus(int32_t n_cu);
 
 /* ABI version of the loaded library (== MISPEC_ABI_VERSION it was built with). */
 int mispec_version(void);

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmispec.so")
 ABLATE_LIB_PATH = os.path.join(_HERE, "csrc", "libmispec_ablate.so")  # benchmarking build
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3
 
 # enums (mirror include/mispec.h)
@@ -25,6 +25,7 @@ EXPORTS = (
     "mispec_octave_stream_f32",
     "mispec_octave_stream_plan_of",
     "mispec_version",
+    "mispec_set_plan_cus",
     "mispec_last_error",
     "mispec_framed_gemm_f32",
     "mispec_framed_gemm_f32_ref",
@@ -481,6 +482,8 @@ def _load(path, how):
     lib.mispec_octave_stream_plan_of.restype = ctypes.c_int
     lib.mispec_octave_stream_plan_of.argtypes = [ctypes.POINTER(OctaveStreamArgs), ctypes.c_int32,
                                                  ctypes.POINTER(OctaveStreamPlan)]
+    lib.mispec_set_plan_cus.restype = ctypes.c_int32
+    lib.mispec_set_plan_cus.argtypes = [ctypes.c_int32]
     v = lib.mispec_version()
     if v != ABI_VERSION:
         raise MispecError("libmispec ABI version %d, expected %d" % (v, ABI_VERSION))

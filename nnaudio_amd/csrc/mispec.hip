@@ -2402,7 +2402,13 @@ bool strip_plan_cached(const KParams &p, const int32_t *sup, int n_cu, StripPlan
   return e.ok;
 }
 
+// the compute units the launch plans are sized for: the device's own count, or the count set with
+// mispec_set_plan_cus (0: none).  Every CU-derived plan reads it here, through device_cus().
+std::atomic<int> g_plan_cus{0};
+
 int device_cus() {
+  const int forced = g_plan_cus.load(std::memory_order_relaxed);
+  if (forced > 0) return forced;
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) {
     int v = 0;
@@ -3446,6 +3452,11 @@ int mispec_device_cus() { return device_cus(); }
 extern "C" {
 
 int mispec_version(void) { return MISPEC_ABI_VERSION; }
+
+int32_t mispec_set_plan_cus(int32_t n_cu) {
+  if (n_cu < 0 || n_cu > 4096) return fail(MISPEC_E_INVALID, "plan CU count must be 0 (the device's) or 1 .. 4096%s");
+  return g_plan_cus.exchange(n_cu);
+}
 
 const char *mispec_last_error(void) { return g_err; }
 

@@ -6,6 +6,7 @@ eager / torch fallback and a missing extension raises.  CPU tensors are served b
 host entries (``mispec_*_host_f32``: the same arithmetic on the calling thread) for every forward
 path -- STFT / filterbank / CQT / MFCC forward and the inverse STFT; backward on CPU tensors raises.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -75,6 +76,29 @@ def set_fft(enabled):
 
 def fft_enabled():
     return _fft
+
+
+@contextlib.contextmanager
+def plan_cus(n_cu):
+    """Size every CU-derived launch plan (persistent grids, per-clip work split, strip / fold plans, octave
+    segments) for ``n_cu`` compute units inside the block; 0 = the device's own count.  The previous value
+    comes back on exit, exceptions included (mispec_set_plan_cus: process-wide, not per thread)."""
+    lib = _abi.load()
+    old = lib.mispec_set_plan_cus(int(n_cu))
+    if old < 0:
+        _abi.check(old, lib)
+    try:
+        yield
+    finally:
+        lib.mispec_set_plan_cus(old)
+
+
+def plan_cus_override():
+    """The CU count set for the launch plans (0: the device's own)."""
+    lib = _abi.load()
+    old = lib.mispec_set_plan_cus(0)
+    lib.mispec_set_plan_cus(old)
+    return old
 
 
 _istft_fused = os.environ.get("MISPEC_ISTFT_FUSED", "1") not in ("0", "false", "off")

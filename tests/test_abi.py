@@ -433,3 +433,137 @@ def test_scratch_guard_sees_cached_objects(tmp_path, monkeypatch):
     assert build._cached_remarks(obj, True) is None              # other defines: stale whatever its date
     build._discard(obj)
     assert not os.path.exists(obj) and not os.path.exists(build._sidecar(obj))
+
+
+def test_plan_cus_override_set_read_back_and_restored():
+    """mispec_set_plan_cus: the CU count every launch plan is sized for -- set, read back, restored; host-only."""
+    from nnaudio_amd import _abi, engine
+
+    lib = _abi.load()
+    assert engine.plan_cus_override() == 0
+    try:
+        assert lib.mispec_set_plan_cus(37) == 0
+        assert lib.mispec_set_plan_cus(5) == 37
+        assert engine.plan_cus_override() == 5
+        assert lib.mispec_set_plan_cus(4096) == 5
+        assert lib.mispec_set_plan_cus(0) == 4096
+        assert engine.plan_cus_override() == 0
+        with engine.plan_cus(32):
+            assert engine.plan_cus_override() == 32
+            with engine.plan_cus(1):
+                assert engine.plan_cus_override() == 1
+            assert engine.plan_cus_override() == 32
+        assert engine.plan_cus_override() == 0
+        with pytest.raises(ZeroDivisionError):  # exceptions included
+            with engine.plan_cus(7):
+                1 / 0
+        assert engine.plan_cus_override() == 0
+    finally:
+        lib.mispec_set_plan_cus(0)
+
+
+def test_plan_cus_override_refuses_invalid_counts():
+    from nnaudio_amd import _abi, engine
+
+    lib = _abi.load()
+    for bad in (-1, -256, 4097, 1 << 30, -(1 << 31)):
+        assert lib.mispec_set_plan_cus(bad) == _abi.E_INVALID, bad
+        assert b"plan CU count" in lib.mispec_last_error()
+        assert engine.plan_cus_override() == 0  # (a refused value changes nothing)
+    with engine.plan_cus(9):
+        assert lib.mispec_set_plan_cus(4097) == _abi.E_INVALID
+        assert engine.plan_cus_override() == 9
+    with pytest.raises(_abi.MispecError):
+        with engine.plan_cus(-3):
+            pass
+    assert engine.plan_cus_override() == 0
+
+
+def test_explicit_count_plan_queries_ignore_the_override():
+    """mispec_strip_plan / mispec_octave_stream_plan_of take their CU count as an argument: the process-wide
+    override must not reach them (nor the plan cache they share with the launches)."""
+    from nnaudio_amd import _abi, engine, features
+    from tests.test_octave_stream_cpu import library_plan
+
+    lib = _abi.load()
+    m = features.CQT1992v2(sr=44100, hop_length=512, n_bins=84, bins_per_octave=12, verbose=False)
+    keep = []
+    a, _sup = _plan_args(m, 16, 441000, keep, "bf16x3")
+
+    def strip(n_cu):
+        buf = (ctypes.c_int32 * (1 + 8 * 36))()
+        n = lib.mispec_strip_plan(ctypes.byref(a), n_cu, buf, len(buf))
+        assert n > 0, lib.mispec_last_error()
+        return list(buf[:1 + 36 * n])
+
+    def octave(n_cus):
+        rc, p = library_plan(132300, 512, (192,) * 4, 132300 // 512 + 1, 0, n_cus=n_cus, n_clips=3)
+        assert rc == 0
+        return [getattr(p, f[0]) if not hasattr(getattr(p, f[0]), "__len__") else list(getattr(p, f[0]))
+                for f in p._fields_]
+
+    want = {n: (strip(n), octave(n)) for n in (256, 32, 5)}
+    assert want[256] != want[5]  # (the count matters to both plans: the check below is not vacuous)
+    for cap in (1, 5, 37, 4096):
+        with engine.plan_cus(cap):
+            for n, w in want.items():
+                assert (strip(n), octave(n)) == w, (cap, n)
+    for n, w in want.items():
+        assert (strip(n), octave(n)) == w
+
+
+def test_strip_workspace_does_not_depend_on_the_count():
+    """mispec_framed_gemm_workspace_bytes for the strip kernels under different planning counts.  Whether
+    plan_strip succeeds does not depend on its slot count (mispec.hip plan_strip: n_slots only ranks the
+    feasible groupings), and the workspace of the strip paths is the split / padded signal + job counter
+    (strip16_ws_bytes, the strip32 branch of the query): no term depends on the plan.  So the size is the same
+    under every count, and a launch under another count than the query's can never need more."""
+    from nnaudio_amd import _abi, engine, features
+
+    lib = _abi.load()
+    m = features.CQT1992v2(sr=44100, hop_length=512, n_bins=84, bins_per_octave=12, verbose=False)
+    for precision in ("bf16x3", "fp32"):
+        differ = 0
+        for B, L in ((1, 70000), (3, 70000), (16, 441000), (64, 441000)):
+            keep = []
+            a, _sup = _plan_args(m, B, L, keep, precision)
+            sizes = []
+            plans = []
+            for cap in (1, 5, 32, 37, 256, 4096):
+                with engine.plan_cus(cap):
+                    sizes.append(lib.mispec_framed_gemm_workspace_bytes(ctypes.byref(a)))
+                buf = (ctypes.c_int32 * (1 + 8 * 36))()
+                assert lib.mispec_strip_plan(ctypes.byref(a), cap, buf, len(buf)) > 0
+                plans.append(list(buf))
+            assert sizes[0] > 0 and len(set(sizes)) == 1, (precision, B, sizes)
+            differ += len(set(map(tuple, plans))) > 1
+        assert differ, precision  # (the plans themselves do change with the count)
+
+
+def test_cu_plan_site_table_is_complete():
+    """Every function of nnaudio_amd/csrc that sizes a launch from device_cus() / mispec_device_cus() is named in
+    tests/test_gpu_cu_plans.py SITES (and runs there at capped counts); a new call site fails here until it is."""
+    import glob
+
+    from tests.test_gpu_cu_plans import SITES
+
+    call = re.compile(r"\b(?:mispec_)?device_cus\s*\(\s*\)")
+    head = re.compile(r"^(?!template\b|struct\b|namespace\b|extern\b|typedef\b|using\b|return\b|static_assert\b)"
+                      r"[A-Za-z_][\w:<>,\s\*&]*?\b([A-Za-z_]\w*)\s*\(")
+    found = {}
+    for path in sorted(glob.glob(os.path.join(ROOT, "nnaudio_amd", "csrc", "*"))):
+        if not path.endswith((".hip", ".inl", ".h", ".cpp")):
+            continue
+        fn = None
+        for i, line in enumerate(open(path, encoding="utf-8").read().split("\n"), 1):
+            code = line.split("//")[0]
+            m = head.match(code)
+            if m and not code.rstrip().endswith(";"):
+                fn = m.group(1)
+            if call.search(code) and fn is not None and fn not in ("device_cus", "mispec_device_cus"):
+                found.setdefault(fn, []).append("%s:%d" % (os.path.basename(path), i))
+    assert "launch_fft_cfg" in found and "mispec_octave_stream_f32" in found  # (the scan sees the known sites)
+    missing = {f: where for f, where in found.items() if f not in SITES}
+    assert not missing, "CU-sized launch plans not in test_gpu_cu_plans.SITES: %s" % missing
+    stale = set(SITES) - set(found)
+    assert not stale, "SITES names functions that no longer call device_cus(): %s" % sorted(stale)

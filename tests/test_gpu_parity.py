@@ -422,13 +422,15 @@ def test_cfg3_mel_full_size_sampled():
     assert np.abs(got - want).max() <= 1e-4 * np.abs(want).max()
 
 
-@pytest.mark.parametrize("precision,B", [("fp32", 16), ("bf16x3", 16), ("bf16x3", 64), ("f16x3", 16), ("f16x3", 64)])
+@pytest.mark.parametrize("precision,B", [("fp32", 16), ("fp32", 64), ("bf16x3", 16), ("bf16x3", 64), ("f16x3", 16),
+                                         ("f16x3", 64)])
 def test_cfg4_cqt1992v2_full_size_sampled(precision, B):
     from nnaudio_amd import features
     from oracle import spectral_oracle as O
 
     # B = 16: one rank's shard of cfg4 (128 clips over 8 GPUs); B = 64: the bench's CQT84 batch,
-    # where the frame tiles alone fill the chip and every workgroup walks all its row tiles
+    # where the frame tiles alone fill the chip and every workgroup walks all its row tiles (fp32, 64:
+    # the launch geometry of the bench's default module)
     L = 441000
     x = torch.randn(B, L, generator=torch.Generator().manual_seed(2))
     m = features.CQT1992v2(sr=44100, hop_length=512, fmin=32.70, n_bins=84, bins_per_octave=12,
