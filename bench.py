@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the spectrogram hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and no more: it sets up, pre-warms, runs the W warm-up and the K timed
+steps, writes --dump-outputs if given and prints the line (metric, value, unit, ms_per_step, dtype, config, "paths"
+with the timed arithmetic alone, and "roofline" priced on the timed steps' own device time, traffic null).  The rest
+of what is described below -- the other arithmetics, "extra", "gather", "roofline_cqt84", live traffic, the dominant
+kernel timed alone, the reference's operator sequences on this GPU and the CPU baseline -- takes minutes of runs of
+its own and is measured with ``--full`` only (``--extras``, ``--traffic`` and ``--cpu-baseline`` switch parts of it).
 
 One "step" = one forward of the hot path over one batch of synthetic waveforms already
 resident in HBM.  Workload at every N (weak scaling, per-GPU work fixed) is BASELINE.json's
@@ -14,7 +21,7 @@ The step is the STFT module as it ships: its kernels are window x DFT (freq_scal
 library evaluates every frame's DFT as an fp32 FFT (csrc/stft_fft.inl; one streaming pass: clips in,
 spectrogram out) -- "roofline" prices it against the HBM roofline on the contract's algorithmic bytes.
 The contraction kernels the same module uses when the FFT does not apply (trainable / non-linear
-bases, n_fft > 2048) are timed in the same run with the FFT switched off and reported under "paths":
+bases, n_fft > 2048) are timed in a --full run with the FFT switched off and reported under "paths":
 "f16x3" (fp32 operands scaled by powers of two and split into (hi, lo) fp16 pairs, three f16 MFMAs per
 product, fp32 accumulate; include/mispec.h MISPEC_PREC_F16X3; ~1e-7 of the spectrum peak), "bf16x3"
 (split bf16, ~5e-6 of the peak) and "fp32" (fp32 MFMA), each with the dynamic range measured on this
@@ -40,7 +47,7 @@ Rank 0 prints ONE JSON line: metric = spectrogram frames/s (whole job), plus
                      used (2500 TFLOP/s bf16 / f16, 157.3 fp32); "frac" <= 1; "algorithmic_frac" = 2 flop per
                      tap of the DENSE contraction the reference performs / time / (peak / MFMAs per product) --
                      it exceeds 1 once symmetric folds skip work, which is why it is not "frac".  The same
-                     matrix-pipe figures of the contraction kernels are under "paths" in every run;
+                     matrix-pipe figures of the contraction kernels are under "paths" in every --full run;
   "roofline_cqt84":  the same block for the other half of BASELINE.json's metric (CQT1992v2,
                      84 bins, B = 64), support-aware useful flops; as the module ships (fp32, default_module: true), with
                      same_bits_as_torch_conv1d = fraction of its complex output on this batch with the same bits as the
@@ -858,29 +865,48 @@ def self_launch(args):
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line.  --extras, --cpu-baseline and --traffic default to what --full says: all on with it,
+    all off without it; given explicitly, they hold either way."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="stft", choices=["stft", "stft4096", "mel", "gammatone", "cqt", "cqt2010", "vqt", "mfcc", "istft"])
-    ap.add_argument("--extras", type=int, default=1,
-                    help="also time the other arithmetics, CQT84, Mel cfg3, Gammatonegram, the cfg5 shard and the gather")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline (minutes): the dominant kernel timed alone, the reference's "
+                         "operator sequence on this GPU, and by default the extras, live traffic and the CPU baseline; "
+                         "without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--extras", type=int, default=None,
+                    help="also time the other arithmetics, CQT84, Mel cfg3, Gammatonegram, the cfg5 shard and the gather "
+                         "(default: 1 with --full, else 0)")
+    ap.add_argument("--cpu-baseline", type=int, default=None, help="(default: 1 with --full, else 0)")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed start-up work before the warm-up steps (GPU out of its idle clocks)")
     ap.add_argument("--precision", default="auto", choices=["auto"] + list(PRECISIONS),
                     help="arithmetic of every timed module; auto = each module's own default (STFT family "
                          "f16x3, the CQT modules fp32; CQT84 is additionally reported in f16x3 and bf16x3)")
-    ap.add_argument("--traffic", default="live", choices=["live", "off"],
-                    help="live: rocprofv3 PMC passes over a child process (N=1 only); off: null")
+    ap.add_argument("--traffic", default=None, choices=["live", "off"],
+                    help="live: rocprofv3 PMC passes over a child process (N=1 only); off: null "
+                         "(default: live with --full, else off)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one returned (rank 0) as DIR/<workload>.npy: "
                          "float32, at most 64 MB, a fixed seeded sample of a larger output (see dump_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.extras is None:
+        args.extras = int(args.full)
+    if args.cpu_baseline is None:
+        args.cpu_baseline = int(args.full)
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "off"
+    return args
+
+
+def main():
+    args = parse_args()
     forced = None if args.precision == "auto" else args.precision
 
     if args.pmc_child:
@@ -1001,7 +1027,7 @@ def main():
         del last
     paths = {prec: primary}
     dominant = None
-    if args.workload == "stft":
+    if args.full and args.workload == "stft":
         dominant = dominant_kernel(prec)
     if args.extras and args.workload == "stft":
         for other in PRECISIONS:
@@ -1292,7 +1318,7 @@ def main():
                 blk["traffic"] = None
                 blk["traffic_detail"] = {"error": repr(e)[:300]}
 
-    if rank == 0 and world == 1 and args.workload == "stft":
+    if args.full and rank == 0 and world == 1 and args.workload == "stft":
         try:  # the reference's operator sequence on THIS device (torch / MIOpen), beside the CPU one below
             out["reference_ops_on_this_gpu"] = reference_ops_on_gpu(make_input(300))
             torch.cuda.empty_cache()
@@ -1311,7 +1337,7 @@ def main():
         except Exception as e:
             out["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": os.cpu_count(),
                                    "kind": "port", "sample": "failed: %r" % (e,)}
-    elif rank == 0:
+    elif rank == 0 and args.cpu_baseline:
         out["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": None, "kind": "port",
                                "sample": "measured at N=1 only"}
 

@@ -3,9 +3,11 @@
 # kernel), CQT84 f16x3 (strip kernel), Mel cfg3 (FFT route).  Summaries go to gpurun_out/r04_summaries/.
 cd /root/repo
 mkdir -p gpurun_out/r04_summaries
-python bench.py > gpurun_out/r04_summaries/bench_r04.log 2>&1
-tail -1 gpurun_out/r04_summaries/bench_r04.log > gpurun_out/r04_summaries/bench_r04.json
-cp bench_detail.json gpurun_out/r04_summaries/bench_detail_r04.json 2>/dev/null
+B=${BENCH_OUT:-runs}/r04_bench  # the bench record: a --full run (extras, live traffic, baselines), detail file beside it
+mkdir -p $B
+python bench.py --full > $B/bench_r04.log 2>&1
+tail -1 $B/bench_r04.log > $B/bench_r04.json
+cp bench_detail.json $B/bench_detail_r04.json 2>/dev/null
 for WP in "stft auto fft" "cqt2010 auto stream" "vqt auto stream" "cqt f16x3 f16x3" "mel auto fft" "mfcc auto fft"; do
   set -- $WP
   bash scripts/profile.sh r04_$1_$3 $1 $2 > /dev/null 2>&1

@@ -4,9 +4,11 @@
 cd /root/repo
 export TMPDIR=/tmp
 mkdir -p gpurun_out/r05_summaries
-python bench.py > gpurun_out/r05_summaries/bench_r05.log 2>&1
-tail -1 gpurun_out/r05_summaries/bench_r05.log > gpurun_out/r05_summaries/bench_r05.json
-cp bench_detail.json gpurun_out/r05_summaries/bench_detail_r05.json 2>/dev/null
+B=${BENCH_OUT:-runs}/r05_bench  # the bench record: a --full run (extras, live traffic, baselines), detail file beside it
+mkdir -p $B
+python bench.py --full > $B/bench_r05.log 2>&1
+tail -1 $B/bench_r05.log > $B/bench_r05.json
+cp bench_detail.json $B/bench_detail_r05.json 2>/dev/null
 for WP in "stft auto fft" "mel auto fft" "cqt auto default_fp32" "cqt f16x3 f16x3" "cqt2010 auto stream" "stft4096 auto fft_composite"; do
   set -- $WP
   bash scripts/profile.sh r05_$1_$3 $1 $2 > /dev/null 2>&1

@@ -4,9 +4,11 @@
 cd /root/repo
 export TMPDIR=/tmp
 mkdir -p gpurun_out/r06_summaries
-timeout 900 python bench.py > gpurun_out/r06_summaries/bench_r06.log 2>&1
-tail -1 gpurun_out/r06_summaries/bench_r06.log > gpurun_out/r06_summaries/bench_r06.json
-cp bench_detail.json gpurun_out/r06_summaries/bench_detail_r06.json 2>/dev/null
+B=${BENCH_OUT:-runs}/r06_bench  # the bench record: a --full run (extras, live traffic, baselines), detail file beside it
+mkdir -p $B
+timeout 900 python bench.py --full > $B/bench_r06.log 2>&1
+tail -1 $B/bench_r06.log > $B/bench_r06.json
+cp bench_detail.json $B/bench_detail_r06.json 2>/dev/null
 for WP in "stft auto fft" "mel auto fft" "cqt auto default_fp32_chain" "cqt2010 auto stream" "gammatone auto frame_major"; do
   set -- $WP
   timeout 600 bash scripts/profile.sh r06_$1_$3 $1 $2 > /dev/null 2>&1

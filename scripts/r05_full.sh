@@ -6,5 +6,7 @@ timeout 1500 python -m pytest tests -x -q -m gpu > gpurun_out/$tag/pytest_gpu.lo
 tail -4 gpurun_out/$tag/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/$tag/smoke.log 2>&1
 tail -3 gpurun_out/$tag/smoke.log
-timeout 600 python bench.py > gpurun_out/$tag/bench.log 2>&1
-tail -c 1200 gpurun_out/$tag/bench.log
+B=${BENCH_OUT:-runs}/$tag
+mkdir -p $B
+timeout 600 python bench.py --full > $B/bench.log 2>&1
+tail -c 1200 $B/bench.log

@@ -44,6 +44,17 @@ def test_gpus_n_self_launch_fails_loudly_without_the_gpus():
     assert "GPU(s) visible" in r.stderr + r.stdout
 
 
+def test_plain_run_leaves_everything_beyond_the_headline_to_full():
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "1"])
+    assert (a.full, a.extras, a.cpu_baseline, a.traffic) == (False, 0, 0, "off")
+    a = bench.parse_args(["--full"])
+    assert (a.full, a.extras, a.cpu_baseline, a.traffic) == (True, 1, 1, "live")
+    # an explicit switch holds either way
+    a = bench.parse_args(["--full", "--extras", "0", "--traffic", "off"])
+    assert (a.extras, a.cpu_baseline, a.traffic) == (0, 1, "off")
+    assert bench.parse_args(["--cpu-baseline", "1"]).cpu_baseline == 1
+
+
 def _canned(n_gpus=1):
     """A full result dict of the shape main() builds, with the longest strings the script writes."""
     prose = "x" * 400
