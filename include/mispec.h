@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MISPEC_ABI_VERSION 14
+#define MISPEC_ABI_VERSION 15
 
 enum {
   MISPEC_OK = 0,
@@ -475,6 +475,30 @@ int mispec_overlap_add_f32(const float *frames, int32_t n_clips, int32_t n_frame
 int mispec_istft_fft_f32(const float *spec, int32_t n_clips, int32_t n_freq, int32_t n_frames, int32_t n_fft,
                          const float *window, int32_t hop, int32_t start, float *out, int64_t out_clip_stride,
                          int32_t out_len, void *stream);
+
+/*
+ * Griffin-Lim phase reconstruction ("fast Griffin-Lim", Perraudin et al. 2013; the reference's Griffin_Lim.forward,
+ * griffin_lim.py:105-147).  One iteration is  y = iSTFT(X);  R = STFT(y);  a = R - beta tprev;
+ * X = mag a / (|a| + 1e-16);  tprev = R.  The inverse is mispec_istft_fft_f32 (or its two-launch / contraction forms);
+ * these entries do the rest:
+ *
+ * mispec_griffin_lim_fft_f32: R = STFT(y) and the update in ONE launch.  `args` describes the STFT of y as an FFT-route
+ *   call of mispec_framed_gemm_f32 does (basis_fold2 of the window x DFT basis, hop, pad, pad_mode, automatic tile,
+ *   no_fft = 0, MISPEC_EPI_COMPLEX, all n_fft/2 + 1 bins, out_row_offset 0) with kernel (n_fft) 512, 1024 or 2048 and
+ *   args->out = tprev, the contiguous (n_clips, n_bins, n_frames, 2) state, updated in place: R is stored there.  mag is
+ *   (n_clips, n_bins, n_frames), spec_next the next X in the layout of tprev (it must not alias tprev or mag).  The
+ *   update is computed from R exactly as mispec_griffin_lim_update_f32 computes it: the result is bit-identical to
+ *   mispec_framed_gemm_f32 into a scratch R followed by that call.  MISPEC_E_UNSUPPORTED for every other problem.
+ * mispec_griffin_lim_update_f32: the update alone over n_bins complex elements: rebuilt = R, (n_bins, 2); tprev (n_bins, 2)
+ *   becomes R; mag (n_bins,); spec_next (n_bins, 2).
+ * mispec_griffin_lim_update_host_f32: the same on host pointers (synchronous).
+ */
+int mispec_griffin_lim_fft_f32(const mispec_framed_gemm_args *args, const float *mag, float *spec_next, float beta,
+                               void *stream);
+int mispec_griffin_lim_update_f32(const float *rebuilt, float *tprev, const float *mag, float *spec_next, int64_t n_bins,
+                                  float beta, void *stream);
+int mispec_griffin_lim_update_host_f32(const float *rebuilt, float *tprev, const float *mag, float *spec_next, int64_t n_bins,
+                                       float beta);
 
 /*
  * power_to_db of MFCC (mel.py:263-279), per clip c over its `clip_elems` values (n_mels * n_frames):

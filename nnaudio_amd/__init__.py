@@ -1,5 +1,5 @@
 """nnaudio_amd: MI355X-native spectrogram front-end, drop-in for
-``nnAudio.features.{STFT, MelSpectrogram, Gammatonegram, CQT1992v2 (CQT), CQT2010v2, VQT}``.
+``nnAudio.features.{STFT, MelSpectrogram, Gammatonegram, CQT1992v2 (CQT), CQT2010v2, VQT, Griffin_Lim}``.
 
 ``forward`` routes through the C ABI of ``csrc/libmispec.so`` (hand-written HIP for gfx950).
 """

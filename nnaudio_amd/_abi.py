@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmispec.so")
 ABLATE_LIB_PATH = os.path.join(_HERE, "csrc", "libmispec_ablate.so")  # benchmarking build
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3
 
 # enums (mirror include/mispec.h)
@@ -74,6 +74,9 @@ EXPORTS = (
     "mispec_fir_decimate_host_f32",
     "mispec_power_to_db_host_f32",
     "mispec_istft_host_f32",
+    "mispec_griffin_lim_fft_f32",
+    "mispec_griffin_lim_update_f32",
+    "mispec_griffin_lim_update_host_f32",
 )
 
 
@@ -425,6 +428,15 @@ def _load(path, how):
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
     ]
+    lib.mispec_griffin_lim_fft_f32.restype = ctypes.c_int
+    lib.mispec_griffin_lim_fft_f32.argtypes = [ctypes.POINTER(FramedGemmArgs), ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_float, ctypes.c_void_p]
+    lib.mispec_griffin_lim_update_f32.restype = ctypes.c_int
+    lib.mispec_griffin_lim_update_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_int64, ctypes.c_float, ctypes.c_void_p]
+    lib.mispec_griffin_lim_update_host_f32.restype = ctypes.c_int
+    lib.mispec_griffin_lim_update_host_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_int64, ctypes.c_float]
     lib.mispec_overlap_add_f32.restype = ctypes.c_int
     lib.mispec_overlap_add_f32.argtypes = [
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,

@@ -78,6 +78,19 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+// One Griffin-Lim update (fast Griffin-Lim, Perraudin et al. 2013; reference griffin_lim.py:105-147) of a (bin, frame):
+// R = the STFT of the current waveform there, tp = the previous R, mag = the target magnitude:
+//   a = R - beta tp,   next = mag a / (|a| + 1e-16),   tp <- R  (the caller stores R)
+// The fused flush of stft_fft.inl, griffin_lim_update_kernel and the host loop all call THIS function, so the fused launch
+// is bit-identical to "Complex launch + update kernel" (the operation order is spelled out: no contraction choices left).
+__host__ __device__ __forceinline__ void griffin_lim_update(float re, float im, float tre, float tim, float mag, float beta,
+                                                           float &nre, float &nim) {
+  const float ar = fmaf(-beta, tre, re), ai = fmaf(-beta, tim, im);
+  const float s = mag / (sqrtf(fmaf(ar, ar, ai * ai)) + 1e-16f);
+  nre = ar * s;
+  nim = ai * s;
+}
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // arithmetic of the split kernels (strip, fold): the operands' format
@@ -194,6 +207,11 @@ struct KParams {
   int fft_row_step;   // FFT route: 512 / n_fft for the frames of n_fft = 256 (zero-extended to 512 samples), else 1
   const float *cmb_E;  // FFT route, n_fft = 4096 composite: the even samples' spectrum (n_clips, 1025, n_frames, 2) -- the Complex
                        // 2048-point instance then stores X[k] = E[k] + W^k O[k] and X[2048 - k] instead of its own tile (stft_fft.inl)
+  // FFT route, Griffin-Lim instance (mispec_griffin_lim_fft_f32): `out` is tprev, updated in place; the flush also reads the
+  // magnitude (n_clips, n_bins, n_frames) and writes the next iteration's spectrum (the layout of `out`)
+  const float *gl_mag;
+  float *gl_next;
+  float gl_beta;
   // symmetric fold (framed_fold.inl): as = folded basis, xs = folded frames, Ks = folded taps
   const float *fold_last;  // fp32 folded (even | odd) rows of the bin the pre-pass evaluates, or NULL
   int fold_last_bin;       // that bin, relative to the problem's first bin
@@ -3241,7 +3259,7 @@ int launch_fft_cfg(const KParams &p, hipStream_t stream) {
   constexpr int FT = fft_tile_frames<M, W, FB>();
   const int tiles_per_clip = (p.n_frames + FT - 1) / FT;
   const long long n_tiles = (long long)p.n_clips * tiles_per_clip;
-  constexpr int per_cu = fft_two_per_cu<M, W, FB>() ? 2 : 1;  // co-resident workgroups
+  constexpr int per_cu = fft_per_cu<M, W, FB, CEPI>();  // co-resident workgroups
   const size_t lds_share = 160 * 1024 / per_cu;
   long long grid = n_tiles < per_cu * device_cus() ? n_tiles : per_cu * device_cus();
   grid = (grid + 7) / 8 * 8;
@@ -3301,6 +3319,43 @@ int launch_fft(const KParams &p, hipStream_t stream) {
   return p.K == 2048 ? launch_fft_size<1024>(p, stream)
                      : (p.K == 1024 ? launch_fft_size<512>(p, stream) : launch_fft_size<256>(p, stream));  // (128, 256: zero-extended)
 }
+
+// Griffin-Lim on the FFT route (mispec_griffin_lim_fft_f32): the Complex instance with the update in its tile flush
+int launch_fft_griffin_lim(const KParams &p, hipStream_t stream) {
+  return p.K == 2048 ? launch_fft_cfg<1024, MISPEC_EPI_COMPLEX, false, FFT_CEPI_GRIFFIN_LIM>(p, stream)
+                     : (p.K == 1024 ? launch_fft_cfg<512, MISPEC_EPI_COMPLEX, false, FFT_CEPI_GRIFFIN_LIM>(p, stream)
+                                    : launch_fft_cfg<256, MISPEC_EPI_COMPLEX, false, FFT_CEPI_GRIFFIN_LIM>(p, stream));
+}
+
+// The update alone (mispec_griffin_lim_update_f32: the route that keeps R = STFT(y) in memory): a thread takes two
+// consecutive (bin, frame) elements -- 16-byte accesses to R, tprev and the next spectrum, 8 bytes of the magnitude
+namespace {
+__global__ void __launch_bounds__(256) griffin_lim_update_kernel(const float *__restrict__ rebuilt, float *__restrict__ tprev,
+                                                                 const float *__restrict__ mag, float *__restrict__ next,
+                                                                 long long n, float beta) {
+  const long long pairs = (n + 1) / 2;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < pairs; q += (long long)gridDim.x * 256) {
+    const long long e = 2 * q;
+    float n0r, n0i, n1r, n1i;
+    if (e + 1 < n) {
+      const f32x4u r = *reinterpret_cast<const f32x4u *>(rebuilt + 2 * e);
+      const f32x4u t = *reinterpret_cast<const f32x4u *>(tprev + 2 * e);
+      const float m0 = mag[e], m1 = mag[e + 1];
+      griffin_lim_update(r[0], r[1], t[0], t[1], m0, beta, n0r, n0i);
+      griffin_lim_update(r[2], r[3], t[2], t[3], m1, beta, n1r, n1i);
+      *reinterpret_cast<f32x4u *>(tprev + 2 * e) = r;
+      *reinterpret_cast<f32x4u *>(next + 2 * e) = f32x4u{n0r, n0i, n1r, n1i};
+    } else {  // an odd element count: the last one alone
+      const float rr = rebuilt[2 * e], ri = rebuilt[2 * e + 1];
+      griffin_lim_update(rr, ri, tprev[2 * e], tprev[2 * e + 1], mag[e], beta, n0r, n0i);
+      tprev[2 * e] = rr;
+      tprev[2 * e + 1] = ri;
+      next[2 * e] = n0r;
+      next[2 * e + 1] = n0i;
+    }
+  }
+}
+}  // namespace
 
 // ---------------------------------------------------------------------------------
 // n_fft = 4096 on the FFT route (round 5; VERDICT r4: STFT(n_fft = 4096) fell to the contraction kernels at ~3 x the
@@ -3890,6 +3945,19 @@ int mispec_power_to_db_host_f32(const float *spec, int32_t n_clips, int64_t clip
   return MISPEC_OK;
 }
 
+int mispec_griffin_lim_update_host_f32(const float *rebuilt, float *tprev, const float *mag, float *spec_next, int64_t n_bins,
+                                       float beta) {
+  if (!rebuilt || !tprev || !mag || !spec_next) return fail(MISPEC_E_INVALID, "NULL pointer%s");
+  if (n_bins <= 0) return fail(MISPEC_E_INVALID, "non-positive size%s");
+  for (long long e = 0; e < n_bins; ++e) {
+    const float rr = rebuilt[2 * e], ri = rebuilt[2 * e + 1];
+    griffin_lim_update(rr, ri, tprev[2 * e], tprev[2 * e + 1], mag[e], beta, spec_next[2 * e], spec_next[2 * e + 1]);
+    tprev[2 * e] = rr;
+    tprev[2 * e + 1] = ri;
+  }
+  return MISPEC_OK;
+}
+
 int mispec_istft_host_f32(const float *spec, int32_t n_clips, int32_t n_freq, int32_t n_frames, const float *basis,
                           int32_t n_fft, const float *window, int32_t hop, int32_t start, float *out,
                           int64_t out_clip_stride, int32_t out_len) {
@@ -4240,6 +4308,39 @@ int mispec_istft_fft_f32(const float *spec, int32_t n_clips, int32_t n_freq, int
   else MISPEC_LAUNCH_IOLA(256)
 #undef MISPEC_LAUNCH_IOLA
   if (rc != MISPEC_OK) return rc;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MISPEC_E_HIP, "kernel launch: %s", hipGetErrorString(e));
+  return MISPEC_OK;
+}
+
+int mispec_griffin_lim_fft_f32(const mispec_framed_gemm_args *args, const float *mag, float *spec_next, float beta,
+                               void *stream) {
+  if (!args || !mag || !spec_next) return fail(MISPEC_E_INVALID, "NULL pointer%s");
+  KParams p;
+  int rc = fill_params(args, p);
+  if (rc != MISPEC_OK) return rc;
+  if (!fft_ok(args, p) || p.epilogue != MISPEC_EPI_COMPLEX || p.fb || p.out_fm || p.out_row_offset != 0)
+    return fail(MISPEC_E_UNSUPPORTED, "Griffin-Lim update: an FFT-route Complex STFT (basis_fold2, automatic tile, no_fft = 0, "
+                                      "no filterbank, out_row_offset 0)%s");
+  if ((p.K != 512 && p.K != 1024 && p.K != 2048) || p.n_bins != p.K / 2 + 1)
+    return fail(MISPEC_E_UNSUPPORTED, "Griffin-Lim update: n_fft 512, 1024 or 2048 with all n_fft/2 + 1 bins%s");
+  if (p.out_row_stride != 2LL * p.n_frames || p.out_clip_stride != 2LL * p.n_bins * p.n_frames)
+    return fail(MISPEC_E_UNSUPPORTED, "Griffin-Lim update: contiguous (n_clips, n_bins, n_frames, 2) tprev%s");
+  p.gl_mag = mag;
+  p.gl_next = spec_next;
+  p.gl_beta = beta;
+  return launch_fft_griffin_lim(p, static_cast<hipStream_t>(stream));
+}
+
+int mispec_griffin_lim_update_f32(const float *rebuilt, float *tprev, const float *mag, float *spec_next, int64_t n_bins,
+                                  float beta, void *stream) {
+  if (!rebuilt || !tprev || !mag || !spec_next) return fail(MISPEC_E_INVALID, "NULL device pointer%s");
+  if (n_bins <= 0) return fail(MISPEC_E_INVALID, "non-positive size%s");
+  const long long pairs = (n_bins + 1) / 2;
+  long long grid = (pairs + 255) / 256;
+  grid = grid < 2048 ? grid : 2048;  // (grid-stride loop: 8 workgroups per CU of the MI355X keep the stream going)
+  hipLaunchKernelGGL(griffin_lim_update_kernel, dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream), rebuilt,
+                     tprev, mag, spec_next, (long long)n_bins, beta);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(MISPEC_E_HIP, "kernel launch: %s", hipGetErrorString(e));
   return MISPEC_OK;

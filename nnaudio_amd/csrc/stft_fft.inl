@@ -120,6 +120,20 @@ constexpr int fft_min_waves() {  // waves per SIMD the register allocation must 
   constexpr int W = (EPI == MISPEC_EPI_COMPLEX || EPI == MISPEC_EPI_PHASE_COSSIN) ? 2 : 1;
   return (fft_two_per_cu<M, W, FB>() ? 2 : 1) * fft_waves<M, W>() / 4;
 }
+// Internal CEPI id (never in the header): the Griffin-Lim instance (mispec_griffin_lim_fft_f32) -- the Complex transform of the
+// waveform, whose flush does the phase update instead of storing the tile (see flush_gl in stft_fft_kernel)
+constexpr int FFT_CEPI_GRIFFIN_LIM = -2;
+// ... which runs ONE workgroup per CU: the update operands it requests a step ahead (30 VGPRs at n_fft = 512) do not fit next to
+// the 512-point Complex instance within the 128 VGPRs of two workgroups per CU (it spilled 16 registers there)
+template <int M, int W, bool FB, int CEPI>
+constexpr int fft_per_cu() {
+  return (CEPI != FFT_CEPI_GRIFFIN_LIM && fft_two_per_cu<M, W, FB>()) ? 2 : 1;
+}
+template <int M, int EPI, bool FB, int CEPI>
+constexpr int fft_min_waves_c() {
+  constexpr int W = (EPI == MISPEC_EPI_COMPLEX || EPI == MISPEC_EPI_PHASE_COSSIN) ? 2 : 1;
+  return CEPI == FFT_CEPI_GRIFFIN_LIM ? fft_waves<M, W>() / 4 : fft_min_waves<M, EPI, FB>();
+}
 
 // 16 bytes per lane, global -> LDS at m0 + 16 lane, as instructions: the loads of a frame stay invisible to
 // the compiler's s_waitcnt placement -- with ordinary loads requested before the tile's stores it waited for
@@ -259,14 +273,15 @@ constexpr int fft_tile_frames() {
 
 // M = n_fft / 2; EPI = the epilogue (W = floats per output element: 2 for Complex / Phase as (cos, sin)); FB = with
 // the fused filterbank (p.fb; EPI = MISPEC_EPI_POWER)
-// CEPI >= 0: the n_fft = 4096 composite's second transform (see cmb below), CEPI = the CALLER'S epilogue
+// CEPI >= 0: the n_fft = 4096 composite's second transform (see cmb below), CEPI = the CALLER'S epilogue;
+// CEPI = FFT_CEPI_GRIFFIN_LIM: the Griffin-Lim instance (EPI = MISPEC_EPI_COMPLEX, all M + 1 bins)
 // FM (round 5): FRAME-MAJOR output (mispec_framed_gemm_args.out_frame_major: element (c, bin, t) at
 // out + c out_clip_stride + t out_row_stride + bin; the floats [n_bins, out_row_stride) of a frame's row are zeroed) -- the
 // spectrum leaves the registers of the post-processing directly, 256 contiguous bytes per store instruction, no tile, no
 // flush, no workgroup barrier in the tile loop.  For consumers that contract over the bins of a frame (the dense
 // filterbank of Gammatonegram: the power spectrogram is then the framed operand of the contraction kernels).
 template <int M, int EPI, bool FB, int CEPI = -1, bool FM = false>
-__global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EPI == MISPEC_EPI_PHASE_COSSIN) ? 2 : 1>() * 64), (fft_min_waves<M, EPI, FB>()))
+__global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EPI == MISPEC_EPI_PHASE_COSSIN) ? 2 : 1>() * 64), (fft_min_waves_c<M, EPI, FB, CEPI>()))
     stft_fft_kernel(const KParams p, const int tiles_per_clip) {
   using namespace fftcore;
   constexpr int N = 2 * M, P = M / 64;
@@ -364,6 +379,8 @@ __global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EP
   constexpr bool CMB_OK = CEPI >= 0;
   static_assert(!CMB_OK || (M == 1024 && EPI == MISPEC_EPI_COMPLEX && !FB), "the composite's second transform is the Complex 2048-point instance");
   constexpr bool cmb = CMB_OK;
+  constexpr bool GL = CEPI == FFT_CEPI_GRIFFIN_LIM;
+  static_assert(!GL || (EPI == MISPEC_EPI_COMPLEX && !FB && !FM), "the Griffin-Lim instance is a Complex transform");
   const int n_rows = cmb ? M + 1 : (p.n_bins < M + 1 ? p.n_bins : M + 1);  // rows of the tile that are stored
   // wave-level ordering of the exchange buffer: the LDS executes a wave's instructions in order; only the
   // compiler has to be kept from moving accesses across
@@ -468,6 +485,63 @@ __global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EP
     }
   };
 
+  // ---- Griffin-Lim (mispec_griffin_lim_fft_f32): the tile holds R = STFT(y) of its frames; the flush reads tprev (= p.out) and the
+  // magnitude for the same (bin, frame pair) -- requested at the end of the step that filled the tile, like the composite's E
+  // rows: they travel under the barrier and the next step's first waits --, and stores R into tprev and mag a / (|a| + 1e-16) into
+  // p.gl_next (griffin_lim_update).  A lane reads and writes the same elements: updating tprev in place has no hazard.
+  // (lane = (row r0 + RPI j, frame pair fl), RPI = 128 rows per pass at M = 1024, 64 at M = 512 / 256: 9 / 9 / 5 passes)
+  constexpr int GNIT = GL ? (M + 1 + NW * 64 / (FT * W / 4) - 1) / (NW * 64 / (FT * W / 4)) : 1;
+  f32x4v gq[GNIT];       // tprev of the pair: (re, im) x 2 frames
+  float gm[GNIT][2];     // the magnitude of the pair
+  auto gl_request = [&](int c, int t0) __attribute__((always_inline)) {
+    constexpr int LPR = FT * W / 4, RPI = NW * 64 / LPR;
+    const int fl = (tid % LPR) * (4 / W), r0 = tid / LPR;
+#pragma unroll
+    for (int j = 0; j < GNIT; ++j) {
+      const int k = r0 + RPI * j;
+      gq[j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+      gm[j][0] = gm[j][1] = 0.f;
+      if (k <= M && t0 + fl < T) {
+        const long long e = ((long long)c * (M + 1) + k) * T + t0 + fl;  // element (c, k, t): contiguous (B, M + 1, T[, 2])
+        if (t0 + fl + 1 < T) {
+          const f32x4u v = *reinterpret_cast<const f32x4u *>(p.out + 2 * e);
+          gq[j] = f32x4v{v[0], v[1], v[2], v[3]};
+          gm[j][0] = p.gl_mag[e];
+          gm[j][1] = p.gl_mag[e + 1];
+        } else {
+          gq[j][0] = p.out[2 * e];
+          gq[j][1] = p.out[2 * e + 1];
+          gm[j][0] = p.gl_mag[e];
+        }
+      }
+    }
+  };
+  auto flush_gl = [&](const float *tile, int c, int t0) __attribute__((always_inline)) {
+    constexpr int LPR = FT * W / 4, RPI = NW * 64 / LPR;
+    const int fl = (tid % LPR) * (4 / W), r0 = tid / LPR;
+    if (t0 + fl >= T || MISPEC_DBG(p, 0x1)) return;
+    const bool two = t0 + fl + 1 < T;
+#pragma unroll
+    for (int j = 0; j < GNIT; ++j) {
+      const int k = r0 + RPI * j;
+      if (k > M) continue;
+      const cf *src = reinterpret_cast<const cf *>(tile + k * C + fl * W);
+      const cf r0v = src[0], r1v = src[1];
+      float n0r, n0i, n1r, n1i;
+      griffin_lim_update(r0v.x, r0v.y, gq[j][0], gq[j][1], gm[j][0], p.gl_beta, n0r, n0i);
+      griffin_lim_update(r1v.x, r1v.y, gq[j][2], gq[j][3], gm[j][1], p.gl_beta, n1r, n1i);
+      const long long e = ((long long)c * (M + 1) + k) * T + t0 + fl;
+      float *const dt = p.out + 2 * e, *const dn = p.gl_next + 2 * e;
+      if (two) {
+        *reinterpret_cast<f32x4u *>(dt) = f32x4u{r0v.x, r0v.y, r1v.x, r1v.y};
+        *reinterpret_cast<f32x4u *>(dn) = f32x4u{n0r, n0i, n1r, n1i};
+      } else {
+        *reinterpret_cast<cf *>(dt) = r0v;
+        *reinterpret_cast<cf *>(dn) = cf{n0r, n0i};
+      }
+    }
+  };
+
   // ---- fused filterbank: the band weights packed into LDS (s_fboff[m] = start of filter m's band [lo, hi)), when
   // they fit what the launch reserved; built once by the persistent workgroup
   int *const s_fboff = reinterpret_cast<int *>(smem_raw + ((stft_fft_smem<M, W, FB>() + 15) & ~(size_t)15));
@@ -547,7 +621,7 @@ __global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EP
     for (int z = 0; z < ((blockIdx.x >> 3) & 3); ++z) __builtin_amdgcn_s_sleep(120);
   }
   float *prev_oc = nullptr;  // the tile waiting to be stored
-  int prev_t0 = 0, step = 0;
+  int prev_t0 = 0, prev_c = 0, step = 0;
   const int n_flush_stores = [&]() {
     constexpr int LPR = FT * W / 4, RPI = NW * 64 / LPR;
     const int r_min = wave * 64 / LPR;
@@ -595,6 +669,9 @@ __global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EP
           } else if (cmb) {
             if (had_pre) fft_wait_vm(0);  // (loads and stores of this flush are not counted: as with the fused filterbank)
             flush_cmb(prev_tile, prev_oc, prev_t0);
+          } else if (GL) {
+            if (had_pre) fft_wait_vm(0);  // (as with the composite: this flush's loads and stores are not counted)
+            flush_gl(prev_tile, prev_c, prev_t0);
           } else {
             flush(prev_tile, prev_oc, prev_t0);
             younger += n_flush_stores;
@@ -606,7 +683,7 @@ __global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EP
       FFT_STAMP(1);
       if (!live) continue;
       if (fast && u == 0) {
-        if (!((FB || cmb) && had_pre && prev_oc)) fft_wait_vm(younger);
+        if (!((FB || cmb || GL) && had_pre && prev_oc)) fft_wait_vm(younger);
         FFT_STAMP(2);
         const cf *const plain = buf;
 #pragma unroll
@@ -696,7 +773,7 @@ __global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EP
         // younger operations is what it was)
         // (only the instances with two waves per SIMD: those that run two workgroups per CU live within 128 VGPRs, where
         // the eight values held across the request spill, and have four waves per SIMD to cover the latency anyway)
-        constexpr bool EARLY = fft_min_waves<M, EPI, FB>() <= 2;
+        constexpr bool EARLY = fft_min_waves_c<M, EPI, FB, CEPI>() <= 2;
         cf zmv[EARLY ? P / 2 : 1];
         if constexpr (EARLY) {
 #pragma unroll
@@ -760,11 +837,13 @@ __global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EP
     // (composite: E's rows for THIS tile, used by the flush at the top of the next step -- requested here, behind the transform:
     // held across it they made the instance spill; they travel under the barrier and the next step's waits)
     if (cmb) cmb_request(c, t0);
+    if (GL) gl_request(c, t0);
     FFT_STAMP(11);
     if constexpr (!FM) __syncthreads();  // the tile is complete (two buffers: and the other one has been read out)
     FFT_STAMP(12);
     prev_oc = FM ? nullptr : oc;
     prev_t0 = t0;
+    prev_c = c;
     ++step;
   }
   if (prev_oc) {
@@ -773,6 +852,8 @@ __global__ void __launch_bounds__((fft_waves<M, (EPI == MISPEC_EPI_COMPLEX || EP
       flush_fb(last, prev_oc, prev_t0);
     else if (cmb)
       flush_cmb(last, prev_oc, prev_t0);
+    else if (GL)
+      flush_gl(last, prev_c, prev_t0);
     else
       flush(last, prev_oc, prev_t0);
   }

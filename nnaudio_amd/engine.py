@@ -112,6 +112,18 @@ def set_istft_fused(enabled):
     return old
 
 
+_gl_fused = os.environ.get("MISPEC_GL_FUSED", "1") not in ("0", "false", "off")
+
+
+def set_griffin_lim_fused(enabled):
+    """Griffin-Lim on the FFT route: the forward STFT of every iteration and the phase update in one launch
+    (``mispec_griffin_lim_fft_f32``) where it serves the shape; ``False`` (or ``MISPEC_GL_FUSED=0``) keeps them apart
+    (the Complex STFT into a scratch spectrogram, then ``mispec_griffin_lim_update_f32``).  Returns the previous setting."""
+    global _gl_fused
+    old, _gl_fused = _gl_fused, bool(enabled)
+    return old
+
+
 _octave_stream = os.environ.get("MISPEC_OCTAVE_STREAM", "1") not in ("0", "false", "off")
 
 
@@ -903,11 +915,12 @@ def istft_basis_is_dft(basis, n_freq):
     return bool((basis.detach().double() - want).abs().max().item() <= 4e-7 * 2.0)
 
 
-def istft(spec, basis, window, hop, start, out_len, dft=False):
+def istft(spec, basis, window, hop, start, out_len, dft=False, out=None):
     """Inverse STFT of a (B, F, T, 2) spectrogram with an ``istft_basis``: frame synthesis
     (planar contraction kernel -- or, with ``dft`` = ``istft_basis_is_dft(basis, F)`` and the FFT path
     enabled, an inverse real FFT per frame --, frames stored sample-innermost) + windowed overlap-add with
-    window-sum-square normalisation (stft.py:15-63) -> (B, out_len)."""
+    window-sum-square normalisation (stft.py:15-63) -> (B, out_len); ``out``: a contiguous float32 (B, out_len)
+    tensor to write instead of a fresh one."""
     dev = _require_device(spec, basis, window, host_ok=True)
     spec = _f32(spec, "spectrogram").contiguous()
     basis = _f32(basis, "basis").contiguous()
@@ -917,7 +930,11 @@ def istft(spec, basis, window, hop, start, out_len, dft=False):
     if two != 2 or basis.shape[1] != 2 * F or window.numel() != N:
         raise RuntimeError("istft: spectrogram %s, basis %s, window %s do not fit together"
                            % (tuple(spec.shape), tuple(basis.shape), tuple(window.shape)))
-    out = torch.empty((B, max(int(out_len), 0)), dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty((B, max(int(out_len), 0)), dtype=torch.float32, device=dev)
+    elif (tuple(out.shape) != (B, max(int(out_len), 0)) or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.device != dev):
+        raise RuntimeError("istft: out must be a contiguous float32 (%d, %d) tensor on %s" % (B, out_len, dev))
     if out.numel() == 0:
         return out
     lib = _abi.load()
@@ -945,6 +962,100 @@ def istft(spec, basis, window, hop, start, out_len, dft=False):
                                               int(start), out.data_ptr(), out.stride(0), out.shape[1],
                                               stream))
     return out
+
+
+def griffin_lim_update(rebuilt, tprev, mag, spec_next, beta):
+    """One Griffin-Lim phase update over every (bin, frame) (mispec_griffin_lim_update_f32 / its host loop):
+    ``a = rebuilt - beta tprev``, ``spec_next = mag a / (|a| + 1e-16)``, ``tprev = rebuilt`` (in place).  All
+    contiguous float32 on one device: ``rebuilt``, ``tprev``, ``spec_next`` (..., 2), ``mag`` the same shape without it."""
+    dev = _require_device(rebuilt, tprev, mag, spec_next, host_ok=True)
+    n = mag.numel()
+    for t, want, what in ((rebuilt, 2 * n, "rebuilt"), (tprev, 2 * n, "tprev"), (mag, n, "mag"), (spec_next, 2 * n, "spec_next")):
+        _f32(t, what)
+        if not t.is_contiguous() or t.numel() != want:
+            raise RuntimeError("griffin_lim_update: %s must be contiguous with %d floats" % (what, want))
+    lib = _abi.load()
+    if dev.type == "cpu":
+        _abi.check(lib.mispec_griffin_lim_update_host_f32(rebuilt.data_ptr(), tprev.data_ptr(), mag.data_ptr(),
+                                                          spec_next.data_ptr(), n, float(beta)))
+        return spec_next
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check(lib.mispec_griffin_lim_update_f32(rebuilt.data_ptr(), tprev.data_ptr(), mag.data_ptr(),
+                                                     spec_next.data_ptr(), n, float(beta), stream))
+    return spec_next
+
+
+_gl_route = threading.local()
+
+
+def griffin_lim_route():
+    """Which route the last ``griffin_lim`` call of this thread took for its forward STFTs: "fft-fused" (STFT + update
+    in one launch), "separate" (Complex STFT on any route, then the update kernel), "host", or None (no iteration)."""
+    return getattr(_gl_route, "name", None)
+
+
+def griffin_lim(mag, spec, *, n_iter, beta, inv_basis, dft, window, hop, pad, pad_mode, basis_re, basis_im,
+                precision=None, prep=None):
+    """Fast Griffin-Lim (Perraudin et al. 2013; the reference's Griffin_Lim.forward, griffin_lim.py:105-147) on the
+    library's transforms.  ``mag`` (B, F, T) is the target magnitude, ``spec`` (B, F, T, 2) the initial ``mag x phase``:
+    updated in place to the last iteration's spectrum.  Per iteration, with no host synchronisation:
+      1. y = iSTFT(spec)   (``istft`` with ``inv_basis`` / ``dft``: the fused inverse FFT where it serves the shape)
+      2. R = STFT(y) (Complex; ``basis_re`` / ``basis_im`` = window x DFT, ``prep`` = ``prepare_basis`` operands), then
+         a = R - beta tprev, spec = mag a / (|a| + 1e-16), tprev = R -- one launch on the FFT route
+         (``mispec_griffin_lim_fft_f32``), else the Complex STFT into a scratch R and ``griffin_lim_update``.
+    Returns iSTFT(spec) after ``n_iter`` iterations, (B, N + hop (T - 1) - 2 pad)."""
+    dev = _require_device(mag, spec, inv_basis, window, basis_re, basis_im, host_ok=True)
+    mag = _f32(mag, "magnitude")
+    if not mag.is_contiguous() or not spec.is_contiguous() or tuple(spec.shape) != tuple(mag.shape) + (2,):
+        raise RuntimeError("griffin_lim: contiguous magnitude (B, F, T) and spectrum (B, F, T, 2) expected")
+    B, F, T = mag.shape
+    N = window.numel()
+    out_len = N + hop * (T - 1) - 2 * pad
+    if out_len <= 0:
+        raise RuntimeError("Griffin-Lim: %d frames give no samples to reconstruct (n_fft %d, hop %d, centred: %s)"
+                           % (T, N, hop, pad > 0))
+    y = torch.empty((B, out_len), dtype=torch.float32, device=dev)
+    _gl_route.name = None
+    if n_iter <= 0:
+        return istft(spec, inv_basis, window, hop, pad, out_len, dft=dft, out=y)
+    prep = prep or {}
+    tprev = torch.zeros_like(spec)
+    lib = _abi.load()
+    stft_kw = dict(hop=hop, pad=pad, pad_mode=pad_mode, epilogue=EPI_COMPLEX, im_sign=-1.0, precision=precision, **prep)
+    fused = (dev.type == "cuda" and _gl_fused and fft_enabled() and prep.get("basis_fold2") is not None
+             and N in (512, 1024, 2048) and F == N // 2 + 1)
+    # the argument blocks are built once: every iteration reads y and writes tprev / spec / R at the same addresses
+    a = keep = R = None
+    if fused:
+        a, _, _, keep = _framed_args(y, basis_re, basis_im, out=tprev, **stft_kw)
+    with contextlib.ExitStack() as ctx:
+        stream = None
+        if dev.type == "cuda":
+            ctx.enter_context(torch.cuda.device(dev))
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for _ in range(n_iter):
+            istft(spec, inv_basis, window, hop, pad, out_len, dft=dft, out=y)
+            if fused:
+                rc = lib.mispec_griffin_lim_fft_f32(ctypes.byref(a), mag.data_ptr(), spec.data_ptr(), float(beta), stream)
+                if rc != _abi.E_UNSUPPORTED:
+                    _abi.check(rc, lib)
+                    continue
+                fused = False  # (refused before any device work: this iteration goes the separate way)
+            if R is None:
+                R = torch.empty_like(spec)
+                a, _, _, keep = _framed_args(y, basis_re, basis_im, out=R, **stft_kw)
+            if dev.type == "cpu":
+                _abi.check(lib.mispec_framed_gemm_host_f32(ctypes.byref(a)), lib)
+                _abi.check(lib.mispec_griffin_lim_update_host_f32(R.data_ptr(), tprev.data_ptr(), mag.data_ptr(),
+                                                                  spec.data_ptr(), mag.numel(), float(beta)), lib)
+            else:
+                _abi.check(lib.mispec_framed_gemm_f32(ctypes.byref(a), stream), lib)
+                _abi.check(lib.mispec_griffin_lim_update_f32(R.data_ptr(), tprev.data_ptr(), mag.data_ptr(),
+                                                             spec.data_ptr(), mag.numel(), float(beta), stream), lib)
+        _gl_route.name = "fft-fused" if fused else ("host" if dev.type == "cpu" else "separate")
+        del keep
+    return istft(spec, inv_basis, window, hop, pad, out_len, dft=dft, out=y)
 
 
 class _IstftFn(torch.autograd.Function):

@@ -6,5 +6,6 @@ from .gammatone import Gammatonegram
 from .cqt import CQT1992v2, CQT2010v2, CQT
 from .cqt_freq import CQT1992, CQT2010
 from .vqt import VQT
+from .griffin_lim import Griffin_Lim
 
-__all__ = ["STFT", "iSTFT", "MelSpectrogram", "MFCC", "Gammatonegram", "CQT1992v2", "CQT2010v2", "CQT", "CQT1992", "CQT2010", "VQT"]
+__all__ = ["STFT", "iSTFT", "MelSpectrogram", "MFCC", "Gammatonegram", "CQT1992v2", "CQT2010v2", "CQT", "CQT1992", "CQT2010", "VQT", "Griffin_Lim"]
