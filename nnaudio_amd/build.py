@@ -110,10 +110,10 @@ def _compile(src, obj, ablate, verbose):
         if os.path.exists(tmp):
             os.remove(tmp)
         raise subprocess.CalledProcessError(res.returncode, cmd)
-    if any(v > 0 and k.startswith("octave_stream") for k, v in remarks.items()):
+    if any(v > 0 and k.startswith(("octave_stream", "cqt_chain")) for k, v in remarks.items()):
         traffic = scratch_instructions(tmp)
         for k in list(remarks):
-            if k.startswith("octave_stream") and remarks[k] > 0 and traffic.get(k, 1) == 0:
+            if k.startswith(("octave_stream", "cqt_chain")) and remarks[k] > 0 and traffic.get(k, 1) == 0:
                 remarks[k] = 0  # (a stack slot nobody loads or stores: SGPR spills in VGPR lanes)
     with open(_sidecar(obj) + ".tmp", "w") as f:
         json.dump({"flags": _flags_key(ablate), "scratch": remarks}, f)
@@ -123,8 +123,8 @@ def _compile(src, obj, ablate, verbose):
 
 
 # Kernels that pace LDS-direct loads with hand-stated s_waitcnt vmcnt(n).
-#   framed_* / octave_stream*: scratch traffic inside the K loop sits BETWEEN loads whose count the wait relies on -- a
-#     spilling build of the bf16x3 kernel gave run-to-run different results on the MI355X.  Refused outright.
+#   framed_* / octave_stream* / cqt_chain*: scratch traffic inside the K loop sits BETWEEN loads whose count the wait relies
+#     on -- a spilling build of the bf16x3 kernel gave run-to-run different results on the MI355X.  Refused outright.
 #   stft_fft_* / istft_*: their waits are "at most n operations outstanding, n = the stores issued after the loads": extra
 #     scratch operations behind the loads only make that wait stronger (in-order retirement, probed:
 #     experiments/ldsdma_hazard), so scratch there is slow, not wrong -- but it must not appear unnoticed: refused unless
@@ -146,8 +146,8 @@ def refused_scratch(remarks, ablate):
     for k, v in remarks.items():
         if v <= 0:
             continue
-        if k.startswith(("framed_", "octave_stream")):
-            if ablate and not k.startswith("framed_"):
+        if k.startswith(("framed_", "octave_stream", "cqt_chain")):
+            if ablate and k.startswith("octave_stream"):
                 continue  # (the benchmarking build's extra switches cost the streaming octave kernel a few registers)
             bad[k] = v
         elif k.startswith(("stft_fft_", "istft_")):

@@ -42,9 +42,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
+#include "epilogue.h"
 #include "mispec.h"
 #include "mispec_internal.h"
 
@@ -59,6 +61,22 @@
 #ifndef CH_PRIO
 #define CH_PRIO 1  // 1: the multiplying waves at s_setprio 3 (0.905 ms); 2: the loading waves (0.932); 0: neither (0.910)
 #endif
+// the plan's row-set split (tiles of the first set when two sets hold the bank) and its sub-stages per batch of two-tile runs
+#ifndef CH_SPLIT
+#define CH_SPLIT 4
+#endif
+#ifndef CH_Q2
+#define CH_Q2 4
+#endif
+
+// the batch shapes the kernel is compiled for, N tiles x Q sub-stages (segment word N | Q << 4): chain_plan refuses a bank whose
+// plan needs another one, so the kernel's switch over them has no reachable default
+#define CH_SHAPES(X)                                              \
+  X(1, 1) X(1, 2) X(1, 3) X(1, 4) X(1, 5) X(1, 6) X(1, 7) X(1, 8) \
+  X(2, 1) X(2, 2) X(2, 3) X(2, 4) X(2, 5)                         \
+  X(3, 1) X(3, 2) X(3, 3)                                         \
+  X(4, 1) X(4, 2) X(5, 1) X(5, 2)                                 \
+  X(6, 1) X(7, 1) X(8, 1) X(9, 1) X(10, 1)
 
 namespace {
 
@@ -106,7 +124,7 @@ struct ChainArgs {
   long long out_clip_stride, out_row_stride;
   int out_row_offset;
   int n_sets;
-  int debug;
+  int pad_;  // (a former field, kept: without it stamps, first_wg and set move 8 bytes and the kernel's scalar argument loads change)
   long long *stamps;  // (CH_ABL & 64) phase clock of workgroup 0
   int first_wg[CH_MAXSETS + 1];
   ChainSetDev set[CH_MAXSETS];
@@ -161,39 +179,6 @@ __device__ __forceinline__ void ch_dma16x3(const void *sbase, unsigned v0, unsig
       :
       : "v"(v0), "v"(v1), "v"(v2), "s"(sbase), "s"(d0), "s"(d1), "s"(d2)
       : "memory", "m0");
-}
-
-// the pointwise epilogue of mispec.hip (epilogue_store): same operations in the same order
-__device__ __forceinline__ void ch_epilogue_store(const ChainArgs &p, float *__restrict__ dst, float re, float im) {
-  switch (p.epilogue) {
-    case MISPEC_EPI_COMPLEX:
-      *reinterpret_cast<float2 *>(dst) = make_float2(re, im);
-      break;
-    case MISPEC_EPI_MAGNITUDE:
-      dst[0] = sqrtf(re * re + im * im + p.eps);
-      break;
-    case MISPEC_EPI_POWER: {
-      const float s = re * re + im * im + p.eps;
-      float r;
-      if (p.power == 2.0f && p.eps == 0.f)
-        r = s;
-      else if (p.power == 1.0f)
-        r = sqrtf(s);
-      else
-        r = powf(sqrtf(s), p.power);
-      dst[0] = r;
-    } break;
-    case MISPEC_EPI_PHASE_ATAN2:
-      dst[0] = atan2f(im + 0.0f, re);
-      break;
-    case MISPEC_EPI_PHASE_COSSIN: {
-      const float a = atan2f(im, re);
-      *reinterpret_cast<float2 *>(dst) = make_float2(cosf(a), sinf(a));
-    } break;
-    default:
-      dst[0] = re;
-      break;
-  }
 }
 
 typedef const int __attribute__((address_space(4))) *ch_seg_ptr;  // constant address space: scalar loads
@@ -650,17 +635,13 @@ __global__ void __launch_bounds__(512) cqt_chain_kernel(const ChainArgs a) {
       a.stamps[9 + 2 * sg] = w;
     }
     switch (w & 255) {
-#define CH_CASE(N, Q)                                     \
-  case (N) | ((Q) << 4):                                  \
+#define CH_CASE(N, Q)                       \
+  case (N) | ((Q) << 4):                    \
     mul_segment<N, Q>(acc, bfirst, c, count); \
     break;
-      CH_CASE(1, 1) CH_CASE(1, 2) CH_CASE(1, 3) CH_CASE(1, 4) CH_CASE(1, 5) CH_CASE(1, 6) CH_CASE(1, 7) CH_CASE(1, 8)
-      CH_CASE(2, 1) CH_CASE(2, 2) CH_CASE(2, 3) CH_CASE(2, 4) CH_CASE(2, 5)
-      CH_CASE(3, 1) CH_CASE(3, 2) CH_CASE(3, 3)
-      CH_CASE(4, 1) CH_CASE(4, 2) CH_CASE(5, 1) CH_CASE(5, 2)
-      CH_CASE(6, 1) CH_CASE(7, 1) CH_CASE(8, 1) CH_CASE(9, 1) CH_CASE(10, 1)
+      CH_SHAPES(CH_CASE)
 #undef CH_CASE
-      default:
+      default:  // (not reached: chain_plan emits the shapes of CH_SHAPES only)
         break;
     }
   }
@@ -690,7 +671,7 @@ __global__ void __launch_bounds__(512) cqt_chain_kernel(const ChainArgs a) {
             re *= sc;
             im *= sc;
           }
-          ch_epilogue_store(a, obase + (long long)(a.out_row_offset + bin) * a.out_row_stride, re, im);
+          epilogue_store(a, obase + (long long)(a.out_row_offset + bin) * a.out_row_stride, re, im);
         }
       }
     }
@@ -716,10 +697,12 @@ __global__ void __launch_bounds__(256) chain_pack_kernel(const float *__restrict
   *reinterpret_cast<f32x4 *>(dst + i * (CH_BRICK / 4) + lane * 4) = v;
 }
 
+}  // namespace
+
 // ------------------------------------------------------------------------------------------------------------
 // host: the plan (tiles, row sets, segments per hop, brick order) from the supports
 // ------------------------------------------------------------------------------------------------------------
-struct ChainSetHost {
+struct MISPEC_HIDDEN ChainSetHost {
   int n_tiles = 0;
   int tile[CH_NMAX];
   int lo[CH_NMAX], hi[CH_NMAX];  // sub-stages
@@ -728,7 +711,7 @@ struct ChainSetHost {
   long long cost = 0;  // bricks + a quarter of the single-tile sub-stages (dependent MFMAs issue at 40 / 32 cycles)
 };
 
-struct ChainPlan {
+struct MISPEC_HIDDEN ChainPlan {
   bool ok = false;
   int n_sets = 0;
   ChainSetHost set[CH_MAXSETS];
@@ -738,9 +721,12 @@ struct ChainPlan {
   long long seg_off[CH_HOPS], map_off = 0, brick_off = 0, bytes = 0;
 };
 
-int env_int(const char *name, int dflt) {
-  const char *v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
+namespace {
+
+constexpr bool ch_shape_compiled(int n, int q) {
+#define CH_IS(N, Q) (n == (N) && q == (Q)) ||
+  return CH_SHAPES(CH_IS) false;
+#undef CH_IS
 }
 
 // `want_map`: also list (tile, sub-stage) of every brick (the pack pass only)
@@ -774,7 +760,7 @@ ChainPlan chain_plan(const int32_t *sup, int n_bins, int K, bool want_map) {
   int n_sets = (n_tiles + CH_NMAX - 1) / CH_NMAX;
   if (n_sets > CH_MAXSETS) return pl;
   std::vector<int> first(1, 0);
-  const int split = env_int("MISPEC_CHAIN_SPLIT", 4);
+  const int split = CH_SPLIT;
   if (n_tiles > 4 && split > 0 && split < n_tiles && n_tiles - split <= CH_NMAX && split <= CH_NMAX) {
     first.push_back(split);
   } else {
@@ -783,6 +769,7 @@ ChainPlan chain_plan(const int32_t *sup, int n_bins, int K, bool want_map) {
   first.push_back(n_tiles);
   pl.n_sets = (int)first.size() - 1;
   long long bricks = 0;
+  bool compiled = true;  // (every batch shape is one of CH_SHAPES)
   for (int s = 0; s < pl.n_sets; ++s) {
     ChainSetHost &S = pl.set[s];
     S.n_tiles = first[s + 1] - first[s];
@@ -816,7 +803,7 @@ ChainPlan chain_plan(const int32_t *sup, int n_bins, int K, bool want_map) {
       // Q: what the loading waves can keep up with.  A loading wave issues ceil(Q / 4) ring blocks + ceil(n Q / 4) bricks per
       // batch at ~300 cycles each beside the MFMA stream (3.14's DMA-issue wall) against 128 n Q cycles of MFMAs:
       // n = 2, Q = 5 is (2 + 3) 300 / 1280 = 1.17 (measured 42 cycles per MFMA), Q = 4 is (1 + 2) 300 / 1024 = 0.88
-      const int qmax = n == 2 ? env_int("MISPEC_CHAIN_Q2", 4) : std::min(CH_QMAX, CH_NMAX / n);
+      const int qmax = n == 2 ? CH_Q2 : std::min(CH_QMAX, CH_NMAX / n);
       for (int h = 0; h < CH_HOPS; ++h) {
         const int per_row = 4 * (h + 1);
         std::vector<int> &sg = pl.segs[h];
@@ -832,6 +819,7 @@ ChainPlan chain_plan(const int32_t *sup, int n_bins, int K, bool want_map) {
             if (cnt <= 0) return;
             for (int t = 0; t < cnt; ++t) boffs[h].push_back((int)(bricks - S.brick0) + ((sb - s0) + t * q) * n);
             sb += cnt * q;
+            compiled = compiled && ch_shape_compiled(n, q);
             const int key = n | (q << 4);
             if ((int)sg.size() > S.seg0[h] && (sg.back() & 255) == key && (sg.back() >> 8) + cnt < (1 << 22))
               sg.back() += cnt << 8;
@@ -865,7 +853,7 @@ ChainPlan chain_plan(const int32_t *sup, int n_bins, int K, bool want_map) {
   pl.map_off = off;
   pl.brick_off = (pl.map_off + bricks * 8 + 1023) & ~1023LL;
   pl.bytes = pl.brick_off + (bricks + 12) * CH_BRICK;  // (the request side runs up to 12 bricks past the end)
-  pl.ok = true;
+  pl.ok = compiled;
   return pl;
 }
 
@@ -914,16 +902,15 @@ int mispec_chain_pack_impl(const float *basis_re, const float *basis_im, int64_t
   return MISPEC_OK;
 }
 
-// 1: the chain kernel serves this call; 0: not this route
-int mispec_chain_ok(const mispec_framed_gemm_args *a) {
-  if (!chain_shape_ok(a)) return 0;
-  const ChainPlan pl = chain_plan(a->row_support_host, a->n_bins, a->kernel, false);
-  return (pl.ok && pl.bytes == a->basis_chain_bytes) ? 1 : 0;
+// the plan is a function of (supports, n_bins, kernel) alone: the one built here is the one the bank's blob was packed with
+std::shared_ptr<const ChainPlan> mispec_chain_plan(const mispec_framed_gemm_args *a) {
+  if (!chain_shape_ok(a)) return nullptr;
+  auto pl = std::make_shared<ChainPlan>(chain_plan(a->row_support_host, a->n_bins, a->kernel, false));
+  if (!pl->ok || pl->bytes != a->basis_chain_bytes) return nullptr;
+  return pl;
 }
 
-int mispec_chain_launch(const mispec_framed_gemm_args *a, int debug, void *stream) {
-  const ChainPlan pl = chain_plan(a->row_support_host, a->n_bins, a->kernel, false);
-  if (!pl.ok || pl.bytes != a->basis_chain_bytes) return mispec_fail_msg(MISPEC_E_INVALID, "chain basis does not match this bank");
+int mispec_chain_launch(const mispec_framed_gemm_args *a, const ChainPlan &pl, void *stream) {
   ChainArgs k;
   memset(&k, 0, sizeof(k));
   const int h = a->hop / 64 - 1;
@@ -958,7 +945,6 @@ int mispec_chain_launch(const mispec_framed_gemm_args *a, int debug, void *strea
   k.out_row_stride = a->out_row_stride;
   k.out_row_offset = a->out_row_offset;
   k.n_sets = pl.n_sets;
-  k.debug = debug | env_int("MISPEC_CHAIN_DEBUG", 0);
   for (int s = 0; s < pl.n_sets; ++s) {
     const ChainSetHost &S = pl.set[s];
     k.first_wg[s] = (int)(s * n_groups);

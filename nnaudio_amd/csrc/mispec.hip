@@ -61,6 +61,7 @@
 
 #include "mispec.h"
 #include "mispec_internal.h"
+#include "epilogue.h"
 #include "fft_core.h"
 
 #ifdef MISPEC_ABLATE
@@ -332,51 +333,6 @@ __device__ __forceinline__ const float *frame_ptr(const KParams &p, int c, int t
     if (t >= p.t_r0) return e + p.edge_ll + (long long)(t - p.t_r0) * p.hop;
   }
   return p.x + (long long)c * p.x_clip_stride + ((long long)t * p.hop - p.pad);
-}
-
-// ---------------------------------------------------------------------------------
-// pointwise epilogue on one (bin, frame) pair, shared by the MFMA and the reference kernel
-// ---------------------------------------------------------------------------------
-template <typename P>
-__device__ __forceinline__ void epilogue_store(const P &p, float *__restrict__ dst, float re, float im) {
-  switch (p.epilogue) {
-    case MISPEC_EPI_COMPLEX: {
-      float2 v = make_float2(re, im);
-      *reinterpret_cast<float2 *>(dst) = v;
-    } break;
-    case MISPEC_EPI_MAGNITUDE:
-      dst[0] = sqrtf(re * re + im * im + p.eps);
-      break;
-    case MISPEC_EPI_POWER: {
-      float s = re * re + im * im + p.eps;
-      float r;
-      if (p.power == 2.0f && p.eps == 0.f)
-        r = s;
-      else if (p.power == 1.0f)
-        r = sqrtf(s);
-      else
-        r = powf(sqrtf(s), p.power);
-      dst[0] = r;
-    } break;
-    case MISPEC_EPI_PHASE_ATAN2:
-      dst[0] = atan2f(im + 0.0f, re);
-      break;
-    case MISPEC_EPI_PHASE_COSSIN: {
-      float a = atan2f(im, re);
-      float2 v = make_float2(cosf(a), sinf(a));
-      *reinterpret_cast<float2 *>(dst) = v;
-    } break;
-    default:
-      dst[0] = re;
-      break;
-  }
-}
-
-__device__ __forceinline__ int epilogue_width(int epi) {
-  return (epi == MISPEC_EPI_COMPLEX || epi == MISPEC_EPI_PHASE_COSSIN) ? 2 : 1;
-}
-inline int epilogue_width_host(int epi) {
-  return (epi == MISPEC_EPI_COMPLEX || epi == MISPEC_EPI_PHASE_COSSIN) ? 2 : 1;
 }
 
 // Barrier that publishes LDS-direct (global_load_lds) data.  These loads complete asynchronously
@@ -3203,33 +3159,6 @@ inline float host_sample(const float *x, long long pos, int L, int pad_mode) {
   }
   return (pos >= 0 && pos < L) ? x[pos] : 0.f;
 }
-
-inline void host_epilogue(const mispec_framed_gemm_args *a, float *dst, float re, float im) {
-  switch (a->epilogue) {
-    case MISPEC_EPI_COMPLEX:
-      dst[0] = re;
-      dst[1] = im;
-      break;
-    case MISPEC_EPI_MAGNITUDE:
-      dst[0] = sqrtf(re * re + im * im + a->eps);
-      break;
-    case MISPEC_EPI_POWER: {
-      const float s2 = re * re + im * im + a->eps;
-      dst[0] = (a->power == 2.0f && a->eps == 0.f) ? s2 : (a->power == 1.0f ? sqrtf(s2) : powf(sqrtf(s2), a->power));
-    } break;
-    case MISPEC_EPI_PHASE_ATAN2:
-      dst[0] = atan2f(im + 0.0f, re);
-      break;
-    case MISPEC_EPI_PHASE_COSSIN: {
-      const float ang = atan2f(im, re);
-      dst[0] = cosf(ang);
-      dst[1] = sinf(ang);
-    } break;
-    default:
-      dst[0] = re;
-      break;
-  }
-}
 }  // namespace
 
 // ---------------------------------------------------------------------------------
@@ -3480,25 +3409,85 @@ int launch_fft4096(const KParams &p, const mispec_framed_gemm_args *a, const Fft
   }
   return MISPEC_OK;
 }
-}  // namespace
+
+// ---------------------------------------------------------------------------------
+// the route of a framed contraction: the kernel that serves it, the one plan that kernel needs and the workspace it takes.
+// ONE decision for mispec_framed_gemm_workspace_bytes, mispec_framed_gemm_f32 and mispec_strip_plan.
+// ---------------------------------------------------------------------------------
+enum RouteKind { ROUTE_FFT, ROUTE_FFT4096, ROUTE_FOLD2, ROUTE_FOLD, ROUTE_STRIP16, ROUTE_DENSE16, ROUTE_CHAIN, ROUTE_BF16X3,
+                 ROUTE_STRIP32, ROUTE_TILES };
+
+struct FramedRoute {
+  RouteKind kind;
+  mispec_framed_gemm_args args;  // the arguments the kernel runs with (after the f16x3 downgrade)
+  int n_cu;                      // the CU count the plans are sized for
+  Fft4096Plan fft4096;
+  Fold2Plan fold2;
+  FoldPlan fold;
+  StripPlan strip;  // strip16 / strip32
+  std::shared_ptr<const ChainPlan> chain;
+  long long bytes;  // workspace
+};
 
 // MISPEC_PREC_F16X3 exists on the folded contractions, on the strip kernel and on the staged dense kernel
-// (complex bases of more than 64 bins): every other shape runs in MISPEC_PREC_F32 on the tile kernels
-// (operands prepared for MISPEC_PREC_F16X3 are not offered to them)
-static bool f16_downgrade(const mispec_framed_gemm_args *a, const KParams &p, mispec_framed_gemm_args &local) {
-  if (a->precision != MISPEC_PREC_F16X3 || plan_fold2(a, p).ok || plan_fold(a, p).ok) return false;
-  StripPlan plan;
-  if (strip16_ok(a, p, device_cus(), plan) || dense16_ok(a, p)) return false;
-  local = *a;
-  local.precision = MISPEC_PREC_F32;
-  local.basis_fold2 = nullptr;
-  local.basis_fold2_bytes = 0;
-  local.basis_fold = nullptr;
-  local.basis_fold_bytes = 0;
-  local.basis_split = nullptr;
-  local.basis_split_bytes = 0;
-  return true;
+// (complex bases of more than 64 bins): every other shape runs in MISPEC_PREC_F32 on the chain or the tile kernels
+// (operands prepared for MISPEC_PREC_F16X3 are not offered to them).  n_cu = 0: device_cus().
+FramedRoute route_framed(const mispec_framed_gemm_args *a, const KParams &p, int n_cu) {
+  FramedRoute r{};
+  r.args = *a;
+  if (fft_ok(a, p)) {
+    r.kind = ROUTE_FFT;  // (no workspace)
+    return r;
+  }
+  r.fft4096 = plan_fft4096(a, p);
+  if (r.fft4096.ok) {
+    r.kind = ROUTE_FFT4096;
+    r.bytes = r.fft4096.bytes;
+    return r;
+  }
+  r.n_cu = n_cu > 0 ? n_cu : device_cus();
+  const EdgePlan e = plan_edges(p.n_samples, p.K, p.hop, p.pad, p.n_frames);
+  const SplitPlan sp = plan_split(p, e);
+  if ((r.fold2 = plan_fold2(a, p)).ok) {
+    r.kind = ROUTE_FOLD2;
+    r.bytes = r.fold2.ws_bytes;
+  } else if ((r.fold = plan_fold(a, p)).ok) {
+    r.kind = ROUTE_FOLD;
+    r.bytes = r.fold.ws_bytes;
+  } else if (strip16_ok(a, p, r.n_cu, r.strip)) {
+    r.kind = ROUTE_STRIP16;
+    r.bytes = strip16_ws_bytes(p, sp);
+  } else if (dense16_ok(a, p)) {
+    r.kind = ROUTE_DENSE16;
+    r.bytes = strip16_ws_bytes(p, sp);
+  } else {
+    mispec_framed_gemm_args &x = r.args;
+    if (x.precision == MISPEC_PREC_F16X3) {
+      x.precision = MISPEC_PREC_F32;
+      x.basis_fold2 = nullptr;
+      x.basis_fold2_bytes = 0;
+      x.basis_fold = nullptr;
+      x.basis_fold_bytes = 0;
+      x.basis_split = nullptr;
+      x.basis_split_bytes = 0;
+    }
+    // (the routes above take no chain copy: they need f16x3 or a bank without supports)
+    if ((r.chain = mispec_chain_plan(&x))) {
+      r.kind = ROUTE_CHAIN;  // (no workspace: the chain kernel resolves the virtual padding in its loads)
+    } else if (bf16x3_ok(&x, p)) {
+      r.kind = ROUTE_BF16X3;
+      r.bytes = sp.edge_bytes + sp.bytes;
+    } else if (strip32_ok(&x, p, r.n_cu, r.strip)) {
+      r.kind = ROUTE_STRIP32;
+      r.bytes = sp.edge_bytes + sp.bytes;  // (the padded fp32 copy of the clips)
+    } else {
+      r.kind = ROUTE_TILES;
+      r.bytes = e.stride * p.n_clips * (int64_t)sizeof(float);
+    }
+  }
+  return r;
 }
+}  // namespace
 
 // shared with the other translation units of the library (mispec_internal.h; hidden symbols)
 int mispec_fail_msg(int code, const char *msg) { return fail(code, "%s", msg); }
@@ -3519,35 +3508,7 @@ int64_t mispec_framed_gemm_workspace_bytes(const mispec_framed_gemm_args *args) 
   KParams p;
   int rc = fill_params(args, p);
   if (rc != MISPEC_OK) return rc;
-  if (fft_ok(args, p)) return 0;
-  {
-    const Fft4096Plan f4 = plan_fft4096(args, p);
-    if (f4.ok) return f4.bytes;
-  }
-  mispec_framed_gemm_args local;
-  if (f16_downgrade(args, p, local)) args = &local;
-  if (mispec_chain_ok(args)) return 0;  // (the chain kernel resolves the virtual padding in its loads)
-  const Fold2Plan f2 = plan_fold2(args, p);
-  if (f2.ok) return f2.ws_bytes;
-  const FoldPlan f = plan_fold(args, p);
-  if (f.ok) return f.ws_bytes;
-  const EdgePlan e = plan_edges(p.n_samples, p.K, p.hop, p.pad, p.n_frames);
-  if (bf16x3_ok(args, p)) {
-    const SplitPlan sp = plan_split(p, e);
-    return sp.edge_bytes + sp.bytes;
-  }
-  {
-    StripPlan plan;
-    if (strip16_ok(args, p, device_cus(), plan) || dense16_ok(args, p)) return strip16_ws_bytes(p, plan_split(p, e));
-  }
-  {
-    StripPlan plan;
-    if (strip32_ok(args, p, device_cus(), plan)) {  // the padded fp32 copy of the clips
-      const SplitPlan sp = plan_split(p, e);
-      return sp.edge_bytes + sp.bytes;
-    }
-  }
-  return e.stride * p.n_clips * (int64_t)sizeof(float);
+  return route_framed(args, p, 0).bytes;
 }
 
 int32_t mispec_strip_plan(const mispec_framed_gemm_args *args, int32_t n_cu, int32_t *plan_out,
@@ -3556,13 +3517,13 @@ int32_t mispec_strip_plan(const mispec_framed_gemm_args *args, int32_t n_cu, int
   int rc = fill_params(args, p);
   if (rc != MISPEC_OK) return rc;
   if (n_cu <= 0 || cap < 0 || (cap > 0 && !plan_out)) return fail(MISPEC_E_INVALID, "bad plan buffer%s");
-  mispec_framed_gemm_args local;
-  if (f16_downgrade(args, p, local)) args = &local;
   StripPlan plan;
-  if (args->precision == MISPEC_PREC_F16X3) {
-    if (!strip16_ok(args, p, n_cu, plan)) return 0;
-  } else if (args->precision == MISPEC_PREC_F32) {
-    if (!strip32_ok(args, p, n_cu, plan)) return 0;
+  if (args->precision == MISPEC_PREC_F16X3 || args->precision == MISPEC_PREC_F32) {
+    const FramedRoute r = route_framed(args, p, n_cu);
+    if (r.kind == ROUTE_STRIP16 || r.kind == ROUTE_STRIP32)
+      plan = r.strip;
+    else if (r.kind != ROUTE_CHAIN || !strip32_ok(&r.args, p, n_cu, plan))  // (beside a chain copy: the strip32 plan)
+      return 0;
   } else {
     if (!bf16x3_ok(args, p) || !args->row_support || !args->row_support_host ||
         args->tile != MISPEC_TILE_AUTO || !basis_has_frags(p.n_bins, p.a_im != nullptr))
@@ -3596,44 +3557,33 @@ int mispec_framed_gemm_f32(const mispec_framed_gemm_args *args, void *stream) {
     if (!fft_ok(args, p)) return fail(MISPEC_E_UNSUPPORTED, "out_frame_major: served by the FFT path only (basis_fold2, automatic tile, no_fft = 0)%s");
     return launch_fft_frame_major(p, s);
   }
-  if (fft_ok(args, p)) return launch_fft(p, s);
-  {
-    const Fft4096Plan f4 = plan_fft4096(args, p);
-    if (f4.ok) return launch_fft4096(p, args, f4, s);
-  }
-  mispec_framed_gemm_args local;
-  if (f16_downgrade(args, p, local)) args = &local;
+  const FramedRoute r = route_framed(args, p, 0);
+  if (r.kind == ROUTE_FFT) return launch_fft(p, s);
+  if (r.kind == ROUTE_FFT4096) return launch_fft4096(p, args, r.fft4096, s);
+  args = &r.args;
   if (p.fb && (args->tile != MISPEC_TILE_AUTO || MISPEC_DBG(p, 0x2000)))
     return fail(MISPEC_E_UNSUPPORTED, "fused filterbank needs the automatic tile choice%s");
-  // CQT1992v2 in fp32 with the bank's chain copy: LDS delay lines instead of per-stage frame gathers (cqt_chain.hip)
-  if (mispec_chain_ok(args)) return mispec_chain_launch(args, (p.debug >> 24) & 15, s);
-  const Fold2Plan fold2 = plan_fold2(args, p);
-  if (fold2.ok) return launch_fold2(p, args, fold2, s);
   // the fused filterbank adds into its output: cleared here (in-kernel clearing by the fold's pre-pass --
-  // 32-byte row segments per workgroup -- cost 1 ms on cfg3)
+  // 32-byte row segments per workgroup -- cost 1 ms on cfg3).  (The chain and fold2 routes take no filterbank.)
   if (p.fb && hipMemsetAsync(p.out, 0, (size_t)p.n_clips * p.out_clip_stride * sizeof(float), s) != hipSuccess)
     return fail(MISPEC_E_HIP, "hipMemsetAsync failed%s");
-  const FoldPlan fold = plan_fold(args, p);
-  if (fold.ok) return launch_fold(p, args, fold, s);
-  const bool bf16x3 = bf16x3_ok(args, p);
-  if (!bf16x3) {
-    StripPlan plan;
-    const int n_cu = device_cus();
-    if (strip16_ok(args, p, n_cu, plan)) return launch_strip16(p, args, plan, n_cu, s);
-    if (dense16_ok(args, p)) return launch_dense16(p, args, s);
-    if (strip32_ok(args, p, n_cu, plan)) return launch_strip32(p, args, plan, n_cu, s);
+  switch (r.kind) {
+    // CQT1992v2 in fp32 with the bank's chain copy: LDS delay lines instead of per-stage frame gathers (cqt_chain.hip)
+    case ROUTE_CHAIN: return mispec_chain_launch(args, *r.chain, s);
+    case ROUTE_FOLD2: return launch_fold2(p, args, r.fold2, s);
+    case ROUTE_FOLD: return launch_fold(p, args, r.fold, s);
+    case ROUTE_STRIP16: return launch_strip16(p, args, r.strip, r.n_cu, s);
+    case ROUTE_DENSE16: return launch_dense16(p, args, s);
+    case ROUTE_STRIP32: return launch_strip32(p, args, r.strip, r.n_cu, s);
+    case ROUTE_BF16X3:  // (the bf16x3 kernels read the padded split signal, not the fp32 path's edge workspace)
+      if (plan_bf16x3_rows(p, args->tile).fp32_leftover && (rc = setup_edges(p, args->workspace, args->workspace_bytes, s)) != MISPEC_OK)
+        return rc;
+      rc = setup_split(p, args, s);
+      return rc != MISPEC_OK ? rc : launch_framed_bf16x3(p, args->tile, s, args->row_support_host);
+    default:  // ROUTE_TILES
+      rc = setup_edges(p, args->workspace, args->workspace_bytes, s);
+      return rc != MISPEC_OK ? rc : launch_framed(p, args->tile, s);
   }
-  // (the bf16x3 kernels read the padded split signal, not the fp32 path's edge workspace)
-  if (!bf16x3 || plan_bf16x3_rows(p, args->tile).fp32_leftover) {
-    rc = setup_edges(p, args->workspace, args->workspace_bytes, s);
-    if (rc != MISPEC_OK) return rc;
-  }
-  if (bf16x3) {
-    rc = setup_split(p, args, s);
-    if (rc != MISPEC_OK) return rc;
-    return launch_framed_bf16x3(p, args->tile, s, args->row_support_host);
-  }
-  return launch_framed(p, args->tile, s);
 }
 
 int64_t mispec_basis_split_bytes(int32_t n_bins, int32_t kernel, int32_t has_im) {
@@ -3700,7 +3650,7 @@ int64_t mispec_basis_chain_bytes(const int32_t *row_support_host, int32_t n_bins
     if (lo < 0 || hi < lo || hi > kernel) return fail(MISPEC_E_INVALID, "row_support_host: need 0 <= start <= stop <= kernel%s");
   }
   const int64_t b = mispec_chain_bytes_impl(row_support_host, n_bins, kernel);
-  if (b < 0) return fail(MISPEC_E_UNSUPPORTED, "chain basis: the supports of the 16-row tiles do not nest, or more than 576 bins%s");
+  if (b < 0) return fail(MISPEC_E_UNSUPPORTED, "chain basis: the supports of the 16-row tiles do not nest, or more than 640 bins%s");
   return b;
 }
 
@@ -3870,7 +3820,7 @@ int mispec_framed_gemm_host_f32(const mispec_framed_gemm_args *a) {
   if (rc != MISPEC_OK) return rc;
   if (a->fb) return fail(MISPEC_E_UNSUPPORTED, "host path: no fused filterbank (use mispec_filterbank_host_f32)%s");
   if (p.out_fm) return fail(MISPEC_E_UNSUPPORTED, "out_frame_major: served by the FFT path only%s");
-  const int E = epilogue_width_host(a->epilogue);
+  const int E = epilogue_width(a->epilogue);
   const long long items = (long long)a->n_clips * a->n_bins;
   host_parallel_for(items, [&](long long it) {
     const int c = (int)(it / a->n_bins), f = (int)(it - (long long)c * a->n_bins);
@@ -3900,7 +3850,7 @@ int mispec_framed_gemm_host_f32(const mispec_framed_gemm_args *a) {
           if (wi) im = fmaf(wi[k], v, im);
         }
       }
-      host_epilogue(a, orow + (long long)t * E, re * sc, a->im_sign * im * sc);
+      epilogue_store(*a, orow + (long long)t * E, re * sc, a->im_sign * im * sc);
     }
   });
   return MISPEC_OK;

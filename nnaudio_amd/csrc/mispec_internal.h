@@ -3,6 +3,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 
 #define MISPEC_HIDDEN __attribute__((visibility("hidden")))
 
@@ -19,8 +20,10 @@ constexpr int mispec_split_row_taps(int kernel) { return (kernel + MISPEC_SPLIT_
 
 // cqt_chain.hip: the chain kernel of CQT1992v2's fp32 contraction (basis_chain of mispec_framed_gemm_args)
 struct mispec_framed_gemm_args;
+struct MISPEC_HIDDEN ChainPlan;
 MISPEC_HIDDEN int64_t mispec_chain_bytes_impl(const int32_t *row_support_host, int32_t n_bins, int32_t kernel);
 MISPEC_HIDDEN int mispec_chain_pack_impl(const float *basis_re, const float *basis_im, int64_t basis_row_stride, int32_t n_bins,
                                          int32_t kernel, const int32_t *row_support_host, void *dst, int64_t dst_bytes, void *stream);
-MISPEC_HIDDEN int mispec_chain_ok(const mispec_framed_gemm_args *a);  // 1: the chain kernel serves this call
-MISPEC_HIDDEN int mispec_chain_launch(const mispec_framed_gemm_args *a, int debug, void *stream);
+// the chain kernel's plan when it serves this call (fp32, the bank's chain copy, a shape it covers), else null
+MISPEC_HIDDEN std::shared_ptr<const ChainPlan> mispec_chain_plan(const mispec_framed_gemm_args *a);
+MISPEC_HIDDEN int mispec_chain_launch(const mispec_framed_gemm_args *a, const ChainPlan &pl, void *stream);

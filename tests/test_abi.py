@@ -158,12 +158,18 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
 
 
 def test_no_environment_switch_reaches_the_kernels():
-    """MISPEC_DEBUG used to be OR-ed into every call's ablation bits; nothing reads it now."""
+    """MISPEC_DEBUG used to be OR-ed into every call's ablation bits; nothing reads it now.  Nor does the product library
+    read the environment (the chain kernel's plan once did: its split and batch length are compile-time constants now)."""
     import inspect
+    import subprocess
 
-    from nnaudio_amd import _abi, engine
+    from nnaudio_amd import _abi, build, engine
 
     assert "MISPEC_DEBUG" not in inspect.getsource(engine) + inspect.getsource(_abi)
+    build.build(verbose=False)
+    nm = subprocess.run(["nm", "-D", "--undefined-only", _abi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    imported = {ln.split()[-1].split("@")[0] for ln in nm.splitlines() if ln.strip()}
+    assert not imported & {"getenv", "secure_getenv"}, sorted(imported & {"getenv", "secure_getenv"})
 
 
 def test_needs_grad_sees_dataparallel_replicas():
@@ -415,14 +421,17 @@ def test_scratch_guard_sees_cached_objects(tmp_path, monkeypatch):
 
     from nnaudio_amd import build
 
-    # the allow-list: framed_* / octave_stream* never, stft_fft_* / istft_* only the listed instances within their bytes
+    # the allow-list: framed_* / octave_stream* / cqt_chain* never, stft_fft_* / istft_* only the listed instances within
+    # their bytes
     r = {"framed_fold_kernelENS_7KParamsE": 8, "octave_stream_kernelILi6ELb1EEvNS_3OSPE": 4,
+         "cqt_chain_kernelILb1EEEvNS_9ChainArgsE": 4,
          "stft_fft_kernelILi512ELi2ELb0ELin1EEEvNS_7KParamsEi": 20, "stft_fft_kernelILi1024ELi1ELb0ELin1EEEvNS_7KParamsEi": 4,
          "istft_ola_fft_kernelILi1024EEEvPKfiiS2_iiiPfxiii": 12, "fold2_frames_kernel": 64, "clean": 0}
     bad = build.refused_scratch(r, ablate=False)
     assert set(bad) == {"framed_fold_kernelENS_7KParamsE", "octave_stream_kernelILi6ELb1EEvNS_3OSPE",
-                        "stft_fft_kernelILi1024ELi1ELb0ELin1EEEvNS_7KParamsEi"}
+                        "cqt_chain_kernelILb1EEEvNS_9ChainArgsE", "stft_fft_kernelILi1024ELi1ELb0ELin1EEEvNS_7KParamsEi"}
     assert "octave_stream_kernelILi6ELb1EEvNS_3OSPE" not in build.refused_scratch(r, ablate=True)  # (benchmarking build: warned)
+    assert "cqt_chain_kernelILb1EEEvNS_9ChainArgsE" in build.refused_scratch(r, ablate=True)  # (compiled alike in both builds)
     # the record next to an object
     obj = str(tmp_path / "unit.o")
     assert build._cached_remarks(obj, False) is None             # no object, no record

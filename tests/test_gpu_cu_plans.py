@@ -27,9 +27,7 @@ SITES = {
     "launch_framed_bf16x3": "test_strip_kernels_at_capped_counts (bf16x3)",
     "launch_fold": "test_fold_rounds_rule_at_capped_counts (fold)",
     "launch_fold2": "test_fold_rounds_rule_at_capped_counts (fold2)",
-    "f16_downgrade": "test_strip_kernels_at_capped_counts (f16x3: the strip16 applicability)",
-    "mispec_framed_gemm_workspace_bytes": "test_strip_workspace_sized_under_another_count",
-    "mispec_framed_gemm_f32": "test_strip_kernels_at_capped_counts (f16x3, fp32)",
+    "route_framed": "test_strip_kernels_at_capped_counts (f16x3, fp32), test_strip_workspace_sized_under_another_count",
     "mispec_istft_frames_fft_f32": "test_inverse_fft_at_capped_counts",
     "mispec_istft_fft_f32": "test_inverse_fft_at_capped_counts",
     "mispec_mfcc_tail_f32": "test_mfcc_tail_at_capped_counts",
