@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MISPEC_ABI_VERSION 15
+#define MISPEC_ABI_VERSION 16
 
 enum {
   MISPEC_OK = 0,
@@ -499,6 +499,65 @@ int mispec_griffin_lim_update_f32(const float *rebuilt, float *tprev, const floa
                                   float beta, void *stream);
 int mispec_griffin_lim_update_host_f32(const float *rebuilt, float *tprev, const float *mag, float *spec_next, int64_t n_bins,
                                        float beta);
+
+/*
+ * Combined frequency and periodicity features (the reference's Combined_Frequency_Periodicity / CFP forward,
+ * cfp.py:129-176): per frame of n_fft samples (the signal zero-padded by n_fft / 2 on both sides, frame t at padded
+ * sample t hop, the window centred in the frame)
+ *   s0   = |DFT(window frame)| window_scale                 spec = max(s0, 0) ** g[0]
+ *   odd i < n_layers:   ceps = nl(Re DFT(spec) / sqrt(n_fft), g[i], cut_ceps)
+ *   even i < n_layers:  spec = nl(Re DFT(ceps) / sqrt(n_fft), g[i], cut_spec)
+ *   nl(X, g, c): max(X, 0), bins [0, c) and [n_fft - c, n_fft) zeroed (c == 0: every bin, the reference's [-0:] slice),
+ *                ** g;  (g == 0, the reference's log(max(X, 0) + 1e-8), is not served)
+ *   l0 = fmat s0[:f_cols],  lf = fmat spec[:f_cols],  lq = qmat ceps[:q_cols],  z = lf * lq
+ * in ONE launch: a workgroup takes two consecutive frames of a clip and runs the whole chain on an n_fft-point complex
+ * buffer in LDS (mixed-radix Stockham passes, csrc/cfp_fft.h); from the second transform on the two frames are the real
+ * and the imaginary part of one sequence.
+ * Frames first_frame .. first_frame + n_frames - 1 are computed; out[c, r, t - first_frame] at
+ * c out_clip_stride + r out_row_stride + (t - first_frame).  l0 / lf / lq may be NULL (not stored).
+ *
+ * mispec_cfp_served: 1 when mispec_cfp_f32 serves the problem, else 0: n_fft = 2^a 5^b, even, 16 <= n_fft <= 16000 (one
+ *   complex fp32 buffer of n_fft points + n_fft / 2 + 1 floats in the 160 KB of LDS), window_size <= n_fft, n_out <= 256,
+ *   2 <= n_layers <= 8, log_layer == 0 (no g[i] == 0).
+ * mispec_cfp_twiddles_host: dst (HOST pointer, n_fft x 2 floats) = exp(-2 pi i k / n_fft), k = 0 .. n_fft - 1, evaluated
+ *   in float64 and rounded once; the caller copies it to the device and passes it as `twiddle`.
+ */
+typedef struct mispec_cfp_args {
+  uint32_t struct_size;      /* sizeof(mispec_cfp_args)                                  */
+  int32_t n_fft;             /* N: points per frame and per transform                    */
+  const float *x;            /* (n_clips, n_samples), rows x_clip_stride floats apart    */
+  int64_t x_clip_stride;
+  int32_t n_clips;
+  int32_t n_samples;
+  int32_t hop;
+  int32_t window_size;
+  const float *window;       /* (window_size)                                            */
+  const float *twiddle;      /* (n_fft, 2): mispec_cfp_twiddles_host                     */
+  float window_scale;        /* 1 / ||window||_2                                         */
+  int32_t first_frame;
+  int32_t n_frames;          /* frames computed and stored                               */
+  int32_t n_layers;          /* len(g)                                                   */
+  float g[8];
+  int32_t cut_ceps;          /* tc_idx: cutoff of the odd layers                         */
+  int32_t cut_spec;          /* fc_idx: cutoff of the even layers (i >= 2)               */
+  const float *fmat;         /* (n_out, f_cols) row-major                                */
+  const int32_t *f_support;  /* (n_out, 2): [start, stop) of the non-zeros of each row   */
+  const float *qmat;         /* (n_out, q_cols)                                          */
+  const int32_t *q_support;
+  int32_t f_cols;            /* <= n_fft                                                 */
+  int32_t q_cols;            /* <= n_fft                                                 */
+  int32_t n_out;
+  int32_t reserved;          /* 0                                                        */
+  float *z;                  /* (n_clips, n_out, n_frames)                               */
+  float *l0;                 /* NULL or as z                                             */
+  float *lf;
+  float *lq;
+  int64_t out_clip_stride;
+  int64_t out_row_stride;
+} mispec_cfp_args;
+int mispec_cfp_f32(const mispec_cfp_args *args, void *stream);
+int mispec_cfp_served(int32_t n_fft, int32_t window_size, int32_t n_out, int32_t n_layers, int32_t log_layer);
+int mispec_cfp_twiddles_host(int32_t n_fft, float *dst);
 
 /*
  * power_to_db of MFCC (mel.py:263-279), per clip c over its `clip_elems` values (n_mels * n_frames):

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmispec.so")
 ABLATE_LIB_PATH = os.path.join(_HERE, "csrc", "libmispec_ablate.so")  # benchmarking build
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3
 
 # enums (mirror include/mispec.h)
@@ -77,7 +77,48 @@ EXPORTS = (
     "mispec_griffin_lim_fft_f32",
     "mispec_griffin_lim_update_f32",
     "mispec_griffin_lim_update_host_f32",
+    "mispec_cfp_f32",
+    "mispec_cfp_served",
+    "mispec_cfp_twiddles_host",
 )
+
+
+class CfpArgs(ctypes.Structure):
+    """struct mispec_cfp_args"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("n_fft", ctypes.c_int32),
+        ("x", ctypes.c_void_p),
+        ("x_clip_stride", ctypes.c_int64),
+        ("n_clips", ctypes.c_int32),
+        ("n_samples", ctypes.c_int32),
+        ("hop", ctypes.c_int32),
+        ("window_size", ctypes.c_int32),
+        ("window", ctypes.c_void_p),
+        ("twiddle", ctypes.c_void_p),
+        ("window_scale", ctypes.c_float),
+        ("first_frame", ctypes.c_int32),
+        ("n_frames", ctypes.c_int32),
+        ("n_layers", ctypes.c_int32),
+        ("g", ctypes.c_float * 8),
+        ("cut_ceps", ctypes.c_int32),
+        ("cut_spec", ctypes.c_int32),
+        ("fmat", ctypes.c_void_p),
+        ("f_support", ctypes.c_void_p),
+        ("qmat", ctypes.c_void_p),
+        ("q_support", ctypes.c_void_p),
+        ("f_cols", ctypes.c_int32),
+        ("q_cols", ctypes.c_int32),
+        ("n_out", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("z", ctypes.c_void_p),
+        ("l0", ctypes.c_void_p),
+        ("lf", ctypes.c_void_p),
+        ("lq", ctypes.c_void_p),
+        ("out_clip_stride", ctypes.c_int64),
+        ("out_row_stride", ctypes.c_int64),
+    ]
 
 
 class FramedGemmArgs(ctypes.Structure):
@@ -437,6 +478,12 @@ def _load(path, how):
     lib.mispec_griffin_lim_update_host_f32.restype = ctypes.c_int
     lib.mispec_griffin_lim_update_host_f32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                        ctypes.c_int64, ctypes.c_float]
+    lib.mispec_cfp_f32.restype = ctypes.c_int
+    lib.mispec_cfp_f32.argtypes = [ctypes.POINTER(CfpArgs), ctypes.c_void_p]
+    lib.mispec_cfp_served.restype = ctypes.c_int
+    lib.mispec_cfp_served.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    lib.mispec_cfp_twiddles_host.restype = ctypes.c_int
+    lib.mispec_cfp_twiddles_host.argtypes = [ctypes.c_int32, ctypes.c_void_p]
     lib.mispec_overlap_add_f32.restype = ctypes.c_int
     lib.mispec_overlap_add_f32.argtypes = [
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,

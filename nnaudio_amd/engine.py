@@ -1787,3 +1787,125 @@ def framed_gemm_autograd(x, basis_re, basis_im, **kw):
             float(kw.get("power", 2.0)), kw.get("row_scale"), support,
             resolve_precision(kw.get("precision")))
     return framed_gemm(x, basis_re, basis_im, **kw)
+
+
+# ---------------------------------------------------------------------------------------------- #
+# CFP (features/cfp.py): spectrum -> generalised cepstrum -> ... -> two log-frequency filterbanks
+# ---------------------------------------------------------------------------------------------- #
+_cfp_kernel = os.environ.get("MISPEC_CFP_KERNEL", "1") not in ("0", "false", "off")
+_cfp_route = threading.local()
+CFP_MAX_LAYERS = 8  # g[] of mispec_cfp_args
+
+
+def set_cfp_kernel(enabled):
+    """CFP on CUDA tensors: the whole chain of a pair of frames in one workgroup (``mispec_cfp_f32``) where the
+    library serves the frame length; ``False`` (or ``MISPEC_CFP_KERNEL=0``) runs the composition of torch operators
+    (``cfp_composition``) instead.  Returns the previous setting."""
+    global _cfp_kernel
+    old, _cfp_kernel = _cfp_kernel, bool(enabled)
+    return old
+
+
+def cfp_route():
+    """Which route the last ``cfp`` call of this thread took: "kernel" or "composition" (None: no call yet)."""
+    return getattr(_cfp_route, "name", None)
+
+
+def cfp_served(N, window_size, n_out, g):
+    """Whether ``mispec_cfp_f32`` serves this problem (the library's rule: ``mispec_cfp_served``); ``g``: the layers'
+    exponents."""
+    g = [float(v) for v in np.ravel(g)]
+    return _abi.load().mispec_cfp_served(int(N), int(window_size), int(n_out), len(g), int(any(v == 0 for v in g))) == 1
+
+
+def cfp_operands(h, fmat, qmat, N):
+    """What the CFP kernel needs besides the module's buffers, on their device: the rows' [start, stop) supports of
+    the two filterbanks, 1 / ||h|| (float64 sum of the float32 window) and -- for frame lengths the kernel serves, on
+    CUDA -- the twiddle table ``exp(-2 pi i k / N)``, fp32 rounded from float64 (filled by the library)."""
+    ops = {"f_support": filterbank_support(fmat)[0], "q_support": filterbank_support(qmat)[0],
+           "window_scale": float(1.0 / np.sqrt(np.sum(h.detach().double().cpu().numpy() ** 2))), "twiddle": None}
+    if h.is_cuda and cfp_served(N, h.numel(), fmat.shape[0], [1.0, 1.0]):
+        tw = np.empty((int(N), 2), dtype=np.float32)
+        _abi.check(_abi.load().mispec_cfp_twiddles_host(int(N), tw.ctypes.data))
+        ops["twiddle"] = torch.from_numpy(tw).to(h.device)
+    return ops
+
+
+def _cfp_nl(X, g, cutoff):
+    """relu, the first and the last `cutoff` bins zeroed, ** g; g == 0: log(relu + 1e-8), then the zeroing.  A cutoff of
+    0 zeroes every bin: ``X[..., -0:]`` is the whole axis (the reference's slices, cfp.py:179-190; kept)."""
+    cutoff = int(cutoff)
+    X = torch.log(torch.relu(X) + 1e-8) if g == 0 else torch.relu(X)
+    X[..., :cutoff] = 0
+    X[..., -cutoff:] = 0
+    return X if g == 0 else X.pow(g)
+
+
+def cfp_composition(x, h, fmat, qmat, *, N, hop, g, tc_idx, fc_idx, first_frame, n_frames, outputs=4):
+    """The four steps of CFP as torch operators on ``x``'s device and in ``x``'s floating type (torch.stft, two
+    torch.fft.fft per further layer pair, two matmuls): what CPU tensors and frame lengths outside the kernel's reach
+    run, and the operator sequence the kernel is timed against.  Returns (Z, tfrL0, tfrLF, tfrLQ)[:outputs]."""
+    h = h.to(x.dtype)
+    tfr0 = torch.stft(x, int(N), hop_length=int(hop), win_length=h.numel(), window=h, onesided=False,
+                      pad_mode="constant", return_complex=True)
+    tfr0 = torch.view_as_real(tfr0).pow(2).sum(-1).sqrt() / torch.norm(h)
+    s0 = tfr0.transpose(1, 2)[:, first_frame:first_frame + n_frames]  # (batch, frames, N)
+    spec = torch.relu(s0).pow(g[0])
+    ceps = None
+    scale = float(np.sqrt(N))
+    for i in range(1, len(g)):
+        if i % 2 == 1:
+            ceps = _cfp_nl(torch.fft.fft(spec).real / scale, g[i], tc_idx)
+        else:
+            spec = _cfp_nl(torch.fft.fft(ceps).real / scale, g[i], fc_idx)
+    fm, qm = fmat.to(x.dtype), qmat.to(x.dtype)
+    kf, kq = fm.shape[1], qm.shape[1]
+    tfrLF = torch.matmul(fm, spec[:, :, :kf].transpose(1, 2))
+    tfrLQ = torch.matmul(qm, ceps[:, :, :kq].transpose(1, 2))
+    res = (tfrLF * tfrLQ, torch.matmul(fm, s0[:, :, :kf].transpose(1, 2)), tfrLF, tfrLQ)
+    return res[:outputs]
+
+
+def cfp(x, h, fmat, qmat, *, N, hop, g, tc_idx, fc_idx, first_frame, n_frames, outputs=4, operands=None):
+    """CFP of a float32 ``(batch, samples)`` tensor: frames ``first_frame .. first_frame + n_frames`` of the
+    zero-padded signal; returns the first ``outputs`` of (Z, tfrL0, tfrLF, tfrLQ), each ``(batch, n_out, n_frames)``.
+    CUDA tensors whose frame length the library serves (``cfp_served``) take the kernel, everything else
+    ``cfp_composition``; ``cfp_route()`` tells which.  ``operands``: a callable returning ``cfp_operands(...)``
+    (the module's cache)."""
+    n_out = fmat.shape[0]
+    if len(g) < 2:
+        raise ValueError("cfp: g needs at least two exponents")
+    if n_frames <= 0 or x.shape[0] == 0:  # (nothing left after the edge frames are dropped)
+        _cfp_route.name = "composition"
+        return tuple(torch.zeros((x.shape[0], n_out, 0), dtype=x.dtype, device=x.device) for _ in range(outputs))
+    use_kernel = (x.is_cuda and _cfp_kernel and not compiling() and len(g) <= CFP_MAX_LAYERS and h.is_cuda and cfp_served(N, h.numel(), n_out, g))
+    if not use_kernel:
+        _cfp_route.name = "composition"
+        return cfp_composition(x, h, fmat, qmat, N=N, hop=hop, g=g, tc_idx=tc_idx, fc_idx=fc_idx,
+                               first_frame=first_frame, n_frames=n_frames, outputs=outputs)
+    ops = operands() if operands is not None else cfp_operands(h, fmat, qmat, N)
+    x = x.contiguous()
+    B, L = x.shape
+    outs = [torch.empty((B, n_out, n_frames), dtype=torch.float32, device=x.device) for _ in range(outputs)]
+    a = _abi.CfpArgs()
+    a.struct_size = ctypes.sizeof(_abi.CfpArgs)
+    a.n_fft = int(N)
+    a.x, a.x_clip_stride, a.n_clips, a.n_samples = x.data_ptr(), x.stride(0), B, L
+    a.hop, a.window_size, a.window, a.window_scale = int(hop), h.numel(), h.contiguous().data_ptr(), ops["window_scale"]
+    a.first_frame, a.n_frames = int(first_frame), int(n_frames)
+    a.twiddle = ops["twiddle"].data_ptr()
+    a.n_layers = len(g)
+    for i, v in enumerate(g):
+        a.g[i] = float(v)
+    a.cut_ceps, a.cut_spec = int(tc_idx), int(fc_idx)
+    fm, qm = fmat.contiguous(), qmat.contiguous()
+    a.fmat, a.f_support, a.f_cols = fm.data_ptr(), ops["f_support"].data_ptr(), fm.shape[1]
+    a.qmat, a.q_support, a.q_cols = qm.data_ptr(), ops["q_support"].data_ptr(), qm.shape[1]
+    a.n_out = n_out
+    ptrs = [o.data_ptr() for o in outs] + [None] * (4 - outputs)
+    a.z, a.l0, a.lf, a.lq = ptrs
+    a.out_clip_stride, a.out_row_stride = n_out * n_frames, n_frames
+    with torch.cuda.device(x.device):
+        _abi.check(_abi.load().mispec_cfp_f32(ctypes.byref(a), torch.cuda.current_stream(x.device).cuda_stream))
+    _cfp_route.name = "kernel"
+    return tuple(outs)
