@@ -311,7 +311,7 @@ _lib_ablate = None
 
 def load_ablate():
     """The benchmarking build (``python -m nnaudio_amd.build --ablate``): same entry points, with
-    the ablation / A-B bits of ``reserved`` compiled in.  Never used by the modules."""
+    the ablation bits of ``reserved`` compiled in.  Never used by the modules."""
     global _lib_ablate
     if _lib_ablate is None:
         _lib_ablate = _load(ABLATE_LIB_PATH, "python -m nnaudio_amd.build --ablate")

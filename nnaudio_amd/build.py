@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "mispec.hip")
 OUT = os.path.join(HERE, "csrc", "libmispec.so")
-# benchmarking build: the same source with -DMISPEC_ABLATE (ablation / A-B bits behind
+# benchmarking build: the same source with -DMISPEC_ABLATE (ablation bits behind
 # mispec_framed_gemm_args.reserved); only scripts/kbench.py and scripts/profile.sh load it
 OUT_ABLATE = os.path.join(HERE, "csrc", "libmispec_ablate.so")
 INC = os.path.join(ROOT, "include")

@@ -1,7 +1,23 @@
 // framed_bf16x3_narrow.inl -- hop-periodic bf16x3 kernel for bases with per-row supports (CQT
 // banks): 32-row tiles with super-stage packing.  Included by mispec.hip after
-// framed_bf16x3_slab.inl (whose header explains the hop-periodic K order: tap k = j*hop + 32*s,
-// one LDS slab per sub-stage s).
+// framed_bf16x3.inl (same operands, same epilogue).
+//
+// The hop-periodic ("slab") K order, shared with framed_bf16x3_strip.inl.  With hop % 32 == 0
+// write a tap index as k = j*hop + 32*s (s < hop/32 "sub-stage", j "super-stage").  The 32 taps
+// of stage (s, j) of frame t are the padded samples
+//        slot[(t + j)*hop + 32*s .. +32)
+// i.e. stage (s, j) of frame t and stage (s, j') of frame t + j - j' are the SAME 64 bytes.  So the
+// K loop runs s outer / j inner: for one s the "slab"
+//        X_s[r] = slot[(t0 + r)*hop + 32*s .. +32),     r < BN + C - 1,   C = ceil(Ks / hop)
+// is DMA'd into LDS once and serves all C stages of that s (frame t0 + i reads row i + j), each of
+// which only streams its A tile.  The split waveform is then read about once per workgroup
+// instead of K/hop times from L2 (4x for the n_fft=2048 / hop=512 STFT, 64x for the 84-bin CQT),
+// which is what bounds the staged bf16x3 kernel (its matrix pipe is 5x faster than the fp32 one,
+// its L2 -> LDS path is not).
+//
+// A frame tile may straddle one clip boundary (n_frames >= BN): its columns then form two runs
+// of consecutive frames, each with its own C - 1 extra rows; column j reads slab row
+// j + (C-1)*[j in second run] + super-stage.
 //
 // In a CQT bank the supports are centred and shrink by 2x per octave, so a workgroup that owns
 // many row tiles spends most of its K range with one or two of them active; per-stage masks keep
@@ -22,6 +38,9 @@
 // buffered per X-step; the single barrier sits before the last X-step, when everything has been
 // read from the A buffer (it becomes the target of the DMA two intervals ahead) and the next
 // interval's data has landed, so that its first fragments are read under the last MFMAs.
+
+constexpr int SLAB_SJ = 3;                    // slab DMA instructions per wave, per plane
+constexpr int SLAB_MAX_ROWS = 16 * 8 * SLAB_SJ;  // 384 rows
 
 __device__ __forceinline__ void framed_bf16x3_narrow_body(const KParams &p, const int wg_index,
                                                           const int wg_count) {

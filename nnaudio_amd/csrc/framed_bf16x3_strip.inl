@@ -1,7 +1,7 @@
 // framed_bf16x3_strip.inl -- kernel for bases with per-row supports (CQT banks) whose basis
 // fragments never pass through LDS; split-bf16 (bf16x3) and, same code, fp32 arithmetic.  Included by mispec.hip after framed_fold.inl; the
 // hop-periodic K order (tap k = j*hop + 32*s, one LDS slab per sub-stage s) is explained in
-// framed_bf16x3_slab.inl, the predecessor of this kernel in framed_bf16x3_narrow.inl.
+// the header of framed_bf16x3_narrow.inl, the predecessor of this kernel.
 //
 // The narrow-tile kernel gives a wave 32 rows x 32 frames: four 16-byte LDS fragment reads per
 // three MFMAs (170 B/clk of LDS traffic per CU at full matrix rate -- more than the LDS delivers)

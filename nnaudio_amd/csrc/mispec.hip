@@ -28,22 +28,29 @@
 //
 // The bf16x3 path (MISPEC_PREC_BF16X3: fp32 operands split into bf16 pairs, three
 // v_mfma_f32_32x32x16_bf16 per product) lives in framed_bf16x3.inl (staged 256x256 kernel, split
-// pre-passes, shared epilogue), framed_bf16x3_slab.inl (hop-periodic K order) and
-// framed_bf16x3_narrow.inl (32-row tiles with super-stage packing for CQT banks), all included
-// below; the host side of both paths, the small pointwise kernels (power_to_db, overlap-add) and
-// the extern "C" entry points are at the end of this file.
+// pre-passes, shared epilogue), framed_bf16x3_narrow.inl (hop-periodic K order; 32-row tiles with
+// super-stage packing for CQT banks) and framed_bf16x3_strip.inl, all included below; the host
+// side of both paths, the small pointwise kernels (power_to_db, overlap-add) and the extern "C"
+// entry points are at the end of this file.
 //
-// Ablation / A-B bits ("debug" below) exist only in the benchmarking build (-DMISPEC_ABLATE ->
+// Ablation bits ("debug" below) exist only in the benchmarking build (-DMISPEC_ABLATE ->
 // libmispec_ablate.so, used by scripts/kbench.py and scripts/profile.sh): there `reserved` of
-// mispec_framed_gemm_args selects them (results are WRONG for bits 1-16, 0x40000, 0x80000):
-// 1 no global loads in the K loop, 2 no LDS stores, 4 no barrier, 8 no fragment reads, 16 no MFMAs,
-// 0x100 frame-tile-fastest tile order, 0x800 register-staged instead of LDS-direct loads, 0x1000
-// generic Toeplitz decimator, 0x2000 no pair launch, 0x4000 bf16x3: staged kernel instead of the
-// hop-periodic ones, 0x8000 one slab buffer, 0x20000 masked 192x256 slab tiles instead of narrow
-// tiles, 0x40000 no epilogue, 0x80000 two K stages only, 0x100000 bf16x3: dense (unfolded) kernel,
-// 0x200000 fold: chunks of clips; fold pre-pass: 0x40 no global stores, 0x80 no global loads, 0x200
-// without the last bin; fused filterbank: 0x400 no walk, 0x10000 walk without stores, 0x400000 plain
-// stores instead of atomics; 0x10000000 support-aware fp32 tiles: 32-row MFMA tiles (round 4) instead of 16-row.
+// mispec_framed_gemm_args carries them.  Each switches a piece of ONE kernel off to time the rest
+// (the results are then wrong); none routes a call to another kernel -- route_framed() and the
+// public arguments (tile, no_fft, which prepared bases are handed over) do that in both builds.
+// The whole set is MISPEC_DBG_KNOWN below; fill_params rejects any other bit.
+//   tile kernels (framed_gemm_body, framed_bf16x3.inl, framed_fold.inl), K loop:
+//     0x1 no global loads   0x2 no LDS stores   0x4 no barrier   0x8 no fragment reads   0x10 no MFMAs
+//     0x40000 no epilogue   0x80000 two K stages only (planar bf16x3)
+//   fold pre-pass (framed_fold.inl):  0x40 no global stores   0x80 no global loads   0x200 without the last bin
+//   fused filterbank walk:  0x400 no walk   0x10000 walk without stores   0x400000 plain stores instead of atomics
+//   narrow kernel:  0x8000 one slab buffer (exact results)
+//   strip kernel:  0x8 no slab DMA   0x10 no reduction / epilogue   0x20 no units   0x1000000 print the plan
+//     0x4000000 one workgroup per CU   0x2000000 phase clock of one job, of the pass in bits 0x30000000
+//   FFT kernel (stft_fft.inl):  0x1 no tile stores   0x2 no post-processing   0x4 no FFT passes   0x8 every tile stored onto the first
+//     0x20 workgroups out of phase   0x40 every frame read from the first 8 KB   0x80 no early DMA of the next tile
+//   0x10000000 on its own: no effect.  Scripts pass it so that `reserved` is non-zero, which is what makes
+//     engine.py load the benchmarking build.
 // In the product library MISPEC_DBG() is the constant false (the branches compile away) and a
 // non-zero `reserved` is rejected.
 //
@@ -66,6 +73,8 @@
 
 #ifdef MISPEC_ABLATE
 #define MISPEC_DBG(p, bit) (((p).debug & (bit)) != 0)
+// every bit of the file header's table
+#define MISPEC_DBG_KNOWN (0xff | 0x200 | 0x400 | 0x8000 | 0x10000 | 0x40000 | 0x80000 | 0x400000 | 0x7000000 | 0x30000000)
 #else
 #define MISPEC_DBG(p, bit) (false)
 #endif
@@ -191,7 +200,7 @@ struct KParams {
   const unsigned short *as;  // split basis planes [re_hi | re_lo | im_hi | im_lo], each (n_bins, Ks)
   long long as_plane;
   int Ks;  // taps per split basis row (K rounded up to 32, zero filled)
-  // hop-periodic K order (framed_bf16x3_slab.inl)
+  // hop-periodic K order (framed_bf16x3_narrow.inl)
   int n_super;    // C = ceil(Ks / hop)
   int slab_rows;  // rows of one slab buffer (>= BN + 2*(C-1), multiple of 16)
   int slab_nbuf;  // 1 or 2 slab buffers
@@ -1093,7 +1102,6 @@ __global__ void __launch_bounds__(WM *WN * 64) framed_gemm_kernel(const KParams 
 }
 
 #include "framed_bf16x3.inl"
-#include "framed_bf16x3_slab.inl"
 #include "framed_bf16x3_narrow.inl"
 #include "framed_fold.inl"
 #include "framed_fold2.inl"
@@ -1346,7 +1354,6 @@ long long prepare_tiling(KParams &p) {
   // (rocprofv3 FETCH_SIZE 1.28e6 KB vs 3.64e6 KB per launch): the K/hop-fold re-reads of the
   // waveform hit L2 instead of the Infinity Cache.
   int g = (64 + p.n_tiles_m / 2) / p.n_tiles_m;
-  if MISPEC_DBG(p, 0x100) g = 1 << 20;  // benchmarking: frame-tile-fastest order
   if (g < 1) g = 1;
   if (g > p.n_tiles_n) g = p.n_tiles_n;
   p.n_group = g;
@@ -1415,23 +1422,16 @@ int launch_group_cfg(KParams *ps, int n, hipStream_t stream) {
 
 // LDS-direct loads (global_load_lds_dwordx4) are used for every framed launch.  Their 16-byte
 // pieces only need element (4-byte) alignment at the source: the whole GPU parity suite,
-// including odd hops / pads / clip lengths, was run with this path forced on.  Bit 0x800 of the
-// debug word selects the register-staged loop instead (A/B comparisons in scripts/kbench.py).
-bool glds_ok(const KParams &p) { return !MISPEC_DBG(p, 0x800); }
-
+// including odd hops / pads / clip lengths, runs on this path.
 template <int WM, int WN, int MR, int NR>
 int launch_pick_mask(const KParams &p, bool masked, hipStream_t stream) {
-  const bool g = glds_ok(p);
   if (masked) {
     // every wave owning all row tiles of 32 frames (the TALL shapes): supports at 16-row granularity
     if constexpr (WM == 1 && NR == 1 && MR <= 4)
-      if (g && !p.fb && !MISPEC_DBG(p, 0x10000000))
-        return launch_cfg<WM, WN, MR, NR, BMODE_FRAMED, AMODE_ROWS, true, true, true>(p, stream);
-    if (g) return launch_cfg<WM, WN, MR, NR, BMODE_FRAMED, AMODE_ROWS, true, true>(p, stream);
-    return launch_cfg<WM, WN, MR, NR, BMODE_FRAMED, AMODE_ROWS, true, false>(p, stream);
+      if (!p.fb) return launch_cfg<WM, WN, MR, NR, BMODE_FRAMED, AMODE_ROWS, true, true, true>(p, stream);
+    return launch_cfg<WM, WN, MR, NR, BMODE_FRAMED, AMODE_ROWS, true, true>(p, stream);
   }
-  if (g) return launch_cfg<WM, WN, MR, NR, BMODE_FRAMED, AMODE_ROWS, false, true>(p, stream);
-  return launch_cfg<WM, WN, MR, NR, BMODE_FRAMED, AMODE_ROWS, false, false>(p, stream);
+  return launch_cfg<WM, WN, MR, NR, BMODE_FRAMED, AMODE_ROWS, false, true>(p, stream);
 }
 
 int launch_tile(const KParams &p, int tile, hipStream_t stream) {
@@ -1493,7 +1493,7 @@ int launch_framed(const KParams &p, int tile, hipStream_t stream) {
   if (p.row_scale) r.row_scale = p.row_scale + main_bins;
   r.out_row_offset = p.out_row_offset + main_bins;
   const int rem_rows = rem * rpb;
-  if (rem_rows <= 64 && glds_ok(p) && !MISPEC_DBG(p, 0x2000)) {
+  if (rem_rows <= 64) {
     // one launch: main grid + narrow workgroups for the leftover rows in its tail
     const long long gm = prepare_tiling<2, 2, 2, 2, AMODE_ROWS>(q);
     const long long gr = rem_rows <= 32 ? prepare_tiling<1, 4, 1, 2, AMODE_ROWS>(r)
@@ -2057,12 +2057,11 @@ int launch_bf16x3_cfg(KParams p, hipStream_t stream) {
   return MISPEC_OK;
 }
 
-// ---- hop-periodic (slab) variant: applicability, LDS budget, launch
+// ---- hop-periodic (slab) K order of the narrow kernel: applicability, slab rows / buffers, LDS budget
 template <int WM, int WN, int MR, int NR>
 bool plan_slab(KParams &p, size_t &smem) {
   constexpr int BM = WM * MR * 32;
   constexpr int BN = WN * NR * 32;
-  if MISPEC_DBG(p, 0x4000) return false;  // benchmarking: force the staged kernel
   if (p.hop % KC != 0 || p.Ks < 2 * p.hop || p.n_frames < BN) return false;
   const int C = (p.Ks + p.hop - 1) / p.hop;
   const int rows = (BN + 2 * (C - 1) + 15) / 16 * 16;
@@ -2080,22 +2079,6 @@ bool plan_slab(KParams &p, size_t &smem) {
   p.slab_nbuf = nbuf;
   smem = a + nbuf * slab + tables;
   return true;
-}
-
-template <int WM, int WN, int MR, int NR, bool MASKED>
-int launch_bf16x3_slab_cfg(KParams p, size_t smem, hipStream_t stream) {
-  const long long grid = prepare_bf16x3<WM, WN, MR, NR>(p);
-  if (grid < 0) return fail(MISPEC_E_UNSUPPORTED, "grid too large%s");
-  if (grid == 0) return MISPEC_OK;
-  auto kern = framed_bf16x3_slab_kernel<WM, WN, MR, NR, MASKED>;
-  // the LDS request varies with K / hop: raise the kernel's limit to the device maximum once
-  static std::atomic<unsigned long long> configured{0};
-  int rc = configure_lds(kern, 160 * 1024, configured);
-  if (rc != MISPEC_OK) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(WM * WN * 64), smem, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(MISPEC_E_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return MISPEC_OK;
 }
 
 int launch_bf16x3_narrow(KParams p, size_t smem, hipStream_t stream) {
@@ -2461,8 +2444,7 @@ Bf16x3Rows plan_bf16x3_rows(const KParams &p, int tile) {
   Bf16x3Rows r;
   r.main_bins = (p.n_bins / bins_per_wg) * bins_per_wg;
   if (masked || (p.n_bins - r.main_bins) * rpb > 64) r.main_bins = p.n_bins;
-  r.pair = tile == MISPEC_TILE_AUTO && !masked && r.main_bins > 0 && r.main_bins < p.n_bins &&
-           !MISPEC_DBG(p, 0x2000);
+  r.pair = tile == MISPEC_TILE_AUTO && !masked && r.main_bins > 0 && r.main_bins < p.n_bins;
   r.fp32_leftover = !r.pair && r.main_bins != p.n_bins;
   return r;
 }
@@ -2481,8 +2463,7 @@ int launch_framed_bf16x3(const KParams &p, int tile, hipStream_t stream,
     KParams r = leftover_rows(p, main_bins);
     r.as = p.as + (long long)main_bins * p.Ks;  // same planes, first leftover bin
     const int rem_rows = r.n_bins * rpb;
-    size_t sm_main = bf16x3_smem<4, 2, 2, 4>();
-    const bool slab = false;  // dense 256x256 slab tiles do not fit in 256 VGPRs
+    const size_t sm_main = bf16x3_smem<4, 2, 2, 4>();
     const long long gm = prepare_bf16x3<4, 2, 2, 4>(q);
     // (the fused filterbank lives in the planar epilogue: 64-row tiles for the leftover rows too)
     const bool narrow_rem = rem_rows <= 32 && !p.fb;
@@ -2511,13 +2492,13 @@ int launch_framed_bf16x3(const KParams &p, int tile, hipStream_t stream,
     if (e != hipSuccess) return fail(MISPEC_E_HIP, "kernel launch: %s", hipGetErrorString(e));
     return MISPEC_OK;
   }
-  // Bases with supports (CQT banks): the hop-periodic narrow-tile kernel when the shape allows
-  // (framed_bf16x3_narrow.inl; debug bit 0x20000 selects its predecessor with 192x256 masked
-  // tiles, framed_bf16x3_slab.inl, for A/B measurements).  Otherwise the staged kernel: 256x256 workgroups of 8 waves (two per SIMD, 64x128 per wave; a 4-wave
-  // layout with 128x128 per wave measured 8 % slower and does not fit without scratch).
+  // Bases with supports (CQT banks): the strip kernel when the caller handed over the supports'
+  // host copy and the plan fits, else the hop-periodic narrow-tile kernel when the shape allows
+  // (framed_bf16x3_narrow.inl).  Otherwise the staged kernel: 256x256 workgroups of 8 waves (two
+  // per SIMD, 64x128 per wave; a 4-wave layout with 128x128 per wave measured 8 % slower and does
+  // not fit without scratch).
   size_t sm = 0;
-  if (masked && sup_host && tile == MISPEC_TILE_AUTO && main_bins == p.n_bins && p.job_counter && p.afrag &&
-      !MISPEC_DBG(p, 0x800000)) {  // (A/B runs: the narrow-tile kernel)
+  if (masked && sup_host && tile == MISPEC_TILE_AUTO && main_bins == p.n_bins && p.job_counter && p.afrag) {
     StripPlan plan;
     const int n_cu = device_cus();
     if (strip_plan_cached(q, sup_host, 2 * n_cu, plan)) {
@@ -2539,8 +2520,7 @@ int launch_framed_bf16x3(const KParams &p, int tile, hipStream_t stream,
     }
   }
   if (masked && q.hop <= 64 * KC && plan_slab<2, 4, 3, 2>(q, sm))
-    rc = MISPEC_DBG(p, 0x20000) ? launch_bf16x3_slab_cfg<2, 4, 3, 2, true>(q, sm, stream)  // A/B runs
-                             : launch_bf16x3_narrow(q, sm, stream);
+    rc = launch_bf16x3_narrow(q, sm, stream);
   else
     rc = masked ? launch_bf16x3_cfg<4, 2, 2, 4, true>(q, stream)
                 : launch_bf16x3_cfg<4, 2, 2, 4, false>(q, stream);
@@ -2570,7 +2550,6 @@ struct FoldPlan {
 FoldPlan plan_fold(const mispec_framed_gemm_args *a, const KParams &p) {
   FoldPlan f{};
   if (!a->basis_fold || a->tile != MISPEC_TILE_AUTO) return f;  // (either precision: the planes' format follows it)
-  if (MISPEC_DBG(p, 0x100000)) return f;  // A/B runs: the dense kernel
   if (!p.a_im || p.row_support || (p.K & 1) || p.K < 64) return f;
   if ((long long)p.hop * 8 < p.K) return f;  // folded frames cost 8 B per folded tap and frame
   if (p.K > 8192) return f;                  // the pre-pass assembles 4 frames (4 K bytes each) in LDS
@@ -2592,12 +2571,12 @@ FoldPlan plan_fold(const mispec_framed_gemm_args *a, const KParams &p) {
   return f;
 }
 
-// Pre-pass and contraction alternate on the caller's stream over chunks of clips whose folded frames
-// (~128 MB) stay in the 256 MB Infinity Cache between the pre-pass that writes them and the
-// contraction that reads them.  (Measured on the MI355X, cfg2: running the pre-pass of chunk k+1 on
-// a side stream beside the contraction of chunk k -- its blocks do fit next to the contraction's --
-// was SLOWER than back to back, 0.81 vs 0.78 ms: the contraction loses more to the pre-pass's
-// traffic than the overlap hides.)
+// One pre-pass launch over all clips, then one contraction launch, on the caller's stream.  (Measured on
+// the MI355X, cfg2: alternating the two over chunks of clips whose folded frames, ~128 MB, stay in the
+// Infinity Cache left the pre-pass no faster and the contraction 3 % slower; the pre-pass of chunk k+1
+// on a side stream beside the contraction of chunk k -- its blocks do fit next to the contraction's --
+// was SLOWER than back to back, 0.81 vs 0.78 ms: the contraction loses more to the pre-pass's traffic
+// than the overlap hides.  DESIGN.md 3.5, "Rejected after measuring".)
 int launch_fold(KParams p, const mispec_framed_gemm_args *a, const FoldPlan &f, hipStream_t stream) {
   if (!a->workspace || a->workspace_bytes < f.ws_bytes)
     return fail(MISPEC_E_INVALID, "workspace too small: size it with the *_workspace_bytes query%s");
@@ -2641,71 +2620,44 @@ int launch_fold(KParams p, const mispec_framed_gemm_args *a, const FoldPlan &f, 
   // the epilogues reuse the stage ring (patches: 8 waves x 32 x 132 floats, or the 128 x 260 power
   // tile + band table of the fused filterbank)
   const size_t smem = (size_t)FOLD_NBUF * FOLD_STAGE;
-  // chunk = a whole number of 256-workgroup rounds of the contraction, ~128 MB of folded frames
-  int q = 256;  // frame tiles that make whole rounds: 256 / gcd(256, n_tiles_m)
-  for (int d = p.n_tiles_m; d % 2 == 0 && q > 1; d /= 2) q /= 2;
-  const long long tile_bytes = (long long)FOLD_BN * f.kf * 8;
-  long long per = (128LL << 20) / (q * tile_bytes);
-  per = q * (per > 0 ? per : 1);
-  if (!MISPEC_DBG(p, 0x200000)) per = tn;  // one chunk unless asked (A/B runs): see above
-  long long tile0 = 0;
-  int clip0 = 0;
-  while (tile0 < tn) {
-    // clips whose frames the next `per` frame tiles need (all the rest when little would remain)
-    long long tile1 = tile0 + per;
-    if (tn - tile1 < per / 2) tile1 = tn;
-    long long clip1 = tile1 >= tn ? p.n_clips : (tile1 * FOLD_BN + p.n_frames - 1) / p.n_frames;
-    if (clip1 > p.n_clips) clip1 = p.n_clips;
-    if (clip1 > clip0) {
-      KParams q1 = pre;
-      q1.fold_clip0 = clip0;
-      hipLaunchKernelGGL(fold_frames_kernel,
-                         dim3((unsigned)((p.n_frames + pre_frames - 1) / pre_frames), (unsigned)(clip1 - clip0)),
-                         dim3(256), pre_smem, stream, q1, xf);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return fail(MISPEC_E_HIP, "fold pre-pass launch: %s", hipGetErrorString(e));
-      clip0 = (int)clip1;
+  hipLaunchKernelGGL(fold_frames_kernel, dim3((unsigned)((p.n_frames + pre_frames - 1) / pre_frames), (unsigned)p.n_clips),
+                     dim3(256), pre_smem, stream, pre, xf);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(MISPEC_E_HIP, "fold pre-pass launch: %s", hipGetErrorString(e));
+  KParams q2 = p;
+  q2.n_tiles_n = (int)tn;
+  long long grid = tn * p.n_tiles_m;
+  q2.fold_main = (int)grid;
+  // whole rounds of the device on 256-frame tiles, the frames behind them on 128-frame tiles
+  // (framed_fold_kernel); less than half a round: 128-frame tiles throughout
+  const int n_cu = device_cus();
+  const double rounds = (double)grid / n_cu;
+  long long main_tn = tn;
+  if (rounds <= 0.5) {
+    main_tn = 0;
+  } else if (rounds > 1.0) {
+    const long long whole = (long long)rounds * n_cu / p.n_tiles_m;  // frame tiles of the whole rounds
+    if (whole < tn) {
+      const long long half = (p.n_cols - whole * FOLD_BN + FOLD_BN / 2 - 1) / (FOLD_BN / 2) * p.n_tiles_m;
+      // a 128-frame tile costs ~0.8 of a 256-frame one (measured: the same basis rows staged for
+      // half the MFMAs, the same fill and epilogue latencies)
+      const double tail = 0.8 * (double)half / n_cu;
+      const double mixed = (double)(whole * p.n_tiles_m) / n_cu + (tail > 0.8 ? tail : 0.8);
+      if (mixed < (double)(long long)(rounds + 0.999) - 0.05) main_tn = whole;
     }
-    KParams q2 = p;
-    q2.fold_tile0 = (int)tile0;
-    q2.n_tiles_n = (int)(tile1 - tile0);
-    long long grid = (tile1 - tile0) * p.n_tiles_m;
-    q2.fold_main = (int)grid;
-    if (tile0 == 0 && tile1 == tn &&
-        !MISPEC_DBG(p, 0x8000000)) {
-      // whole rounds of the device on 256-frame tiles, the frames behind them on 128-frame tiles
-      // (framed_fold_kernel); less than half a round: 128-frame tiles throughout
-      const int n_cu = device_cus();
-      const double rounds = (double)grid / n_cu;
-      long long main_tn = tn;
-      if (rounds <= 0.5) {
-        main_tn = 0;
-      } else if (rounds > 1.0) {
-        const long long whole = (long long)rounds * n_cu / p.n_tiles_m;  // frame tiles of the whole rounds
-        if (whole < tn) {
-          const long long half = (p.n_cols - whole * FOLD_BN + FOLD_BN / 2 - 1) / (FOLD_BN / 2) * p.n_tiles_m;
-          // a 128-frame tile costs ~0.8 of a 256-frame one (measured: the same basis rows staged for
-          // half the MFMAs, the same fill and epilogue latencies)
-          const double tail = 0.8 * (double)half / n_cu;
-          const double mixed = (double)(whole * p.n_tiles_m) / n_cu + (tail > 0.8 ? tail : 0.8);
-          if (mixed < (double)(long long)(rounds + 0.999) - 0.05) main_tn = whole;
-        }
-      }
-      if (main_tn < tn) {
-        q2.n_tiles_n = (int)main_tn;
-        q2.fold_main = (int)(main_tn * p.n_tiles_m);
-        q2.fold_tail_frame0 = main_tn * FOLD_BN;
-        const long long tail_tn = (p.n_cols - q2.fold_tail_frame0 + FOLD_BN / 2 - 1) / (FOLD_BN / 2);
-        grid = q2.fold_main + tail_tn * p.n_tiles_m;
-      }
-    }
-    q2.n_group = g > q2.n_tiles_n ? q2.n_tiles_n : g;
-    if (q2.n_group < 1) q2.n_group = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, q2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MISPEC_E_HIP, "kernel launch: %s", hipGetErrorString(e));
-    tile0 = tile1;
   }
+  if (main_tn < tn) {
+    q2.n_tiles_n = (int)main_tn;
+    q2.fold_main = (int)(main_tn * p.n_tiles_m);
+    q2.fold_tail_frame0 = main_tn * FOLD_BN;
+    const long long tail_tn = (p.n_cols - q2.fold_tail_frame0 + FOLD_BN / 2 - 1) / (FOLD_BN / 2);
+    grid = q2.fold_main + tail_tn * p.n_tiles_m;
+  }
+  q2.n_group = g > q2.n_tiles_n ? q2.n_tiles_n : g;
+  if (q2.n_group < 1) q2.n_group = 1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, q2);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(MISPEC_E_HIP, "kernel launch: %s", hipGetErrorString(e));
   return MISPEC_OK;
 }
 
@@ -2729,7 +2681,6 @@ struct Fold2Plan {
 Fold2Plan plan_fold2(const mispec_framed_gemm_args *a, const KParams &p) {
   Fold2Plan f{};
   if (!a->basis_fold2 || a->tile != MISPEC_TILE_AUTO) return f;
-  if (MISPEC_DBG(p, 0x100000) || MISPEC_DBG(p, 0x40000000)) return f;  // A/B runs: dense / single fold
   if (!p.a_im || p.row_support || p.row_scale || p.fb || !fold2_kernel_ok(p.K)) return f;
   if ((long long)p.hop * 8 < p.K) return f;  // the folded frames cost 4 K bytes per frame
   if (a->basis_fold2_bytes < basis_fold2_bytes(p.n_bins, p.K)) return f;
@@ -2912,6 +2863,8 @@ int fill_params(const mispec_framed_gemm_args *a, KParams &p) {
   p.out_row_stride = a->out_row_stride;
   p.out_row_offset = a->out_row_offset;
 #ifdef MISPEC_ABLATE
+  if (a->reserved & ~MISPEC_DBG_KNOWN)
+    return fail(MISPEC_E_INVALID, "reserved: not an ablation bit of this build (see the header of mispec.hip)%s");
   p.debug = a->reserved;
 #else
   if (a->reserved != 0)
@@ -2992,7 +2945,7 @@ int fir_params(KParams &p, const float *x, int64_t x_clip_stride, int32_t n_clip
 // copy of the basis in basis_split): applicability and launch
 bool strip32_ok(const mispec_framed_gemm_args *a, const KParams &p, int n_cu, StripPlan &plan) {
   if (a->precision != MISPEC_PREC_F32 || !a->basis_split || !a->row_support || !a->row_support_host ||
-      !p.a_im || a->tile != MISPEC_TILE_AUTO || p.fb || MISPEC_DBG(p, 0x800000))
+      !p.a_im || a->tile != MISPEC_TILE_AUTO || p.fb)
     return false;
   if (!basis_has_frags(p.n_bins, true) ||
       a->basis_split_bytes < (long long)((p.n_bins + 15) / 16) * round_up_kc(p.K) * 128 + 4096)
@@ -3172,7 +3125,6 @@ inline float host_sample(const float *x, long long pos, int L, int pad_mode) {
 // ---------------------------------------------------------------------------------
 bool fft_ok(const mispec_framed_gemm_args *a, const KParams &p) {
   if (!a->basis_fold2 || a->tile != MISPEC_TILE_AUTO || a->no_fft) return false;
-  if (MISPEC_DBG(p, 0x100000) || MISPEC_DBG(p, 0x40000000) || MISPEC_DBG(p, 0x08000000)) return false;  // A/B runs
   if (!p.a_im || p.row_support || p.row_scale || !fold2_kernel_ok(p.K)) return false;
   if (p.fb && (p.epilogue != MISPEC_EPI_POWER || p.out_row_offset != 0)) return false;  // (fused filterbank: in the tile flush)
   if (a->basis_fold2_bytes < basis_fold2_bytes(p.n_bins, p.K)) return false;
@@ -3309,7 +3261,6 @@ struct Fft4096Plan {
 Fft4096Plan plan_fft4096(const mispec_framed_gemm_args *a, const KParams &p) {
   Fft4096Plan pl = {};
   if (!a->basis_fold2 || a->tile != MISPEC_TILE_AUTO || a->no_fft || p.K != 4096) return pl;
-  if (MISPEC_DBG(p, 0x100000) || MISPEC_DBG(p, 0x40000000) || MISPEC_DBG(p, 0x08000000)) return pl;  // A/B runs
   if (!p.a_im || p.row_support || p.row_scale || p.fb || (p.hop & 1) || (p.pad & 1)) return pl;
   if (a->basis_fold2_bytes < basis_fold2_bytes(p.n_bins, p.K)) return pl;
   // (the (cos, sin) phase format -- CQT's, never an STFT module's -- spills in the second transform's flush: contraction kernels)
@@ -3561,7 +3512,7 @@ int mispec_framed_gemm_f32(const mispec_framed_gemm_args *args, void *stream) {
   if (r.kind == ROUTE_FFT) return launch_fft(p, s);
   if (r.kind == ROUTE_FFT4096) return launch_fft4096(p, args, r.fft4096, s);
   args = &r.args;
-  if (p.fb && (args->tile != MISPEC_TILE_AUTO || MISPEC_DBG(p, 0x2000)))
+  if (p.fb && args->tile != MISPEC_TILE_AUTO)
     return fail(MISPEC_E_UNSUPPORTED, "fused filterbank needs the automatic tile choice%s");
   // the fused filterbank adds into its output: cleared here (in-kernel clearing by the fold's pre-pass --
   // 32-byte row segments per workgroup -- cost 1 ms on cfg3).  (The chain and fold2 routes take no filterbank.)
@@ -4680,7 +4631,7 @@ int mispec_fir_decimate_f32(const float *x, int64_t x_clip_stride, int32_t n_cli
                       y_clip_stride, n_out);
   if (rc != MISPEC_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (stride == 2 && n_taps + 62 <= 8 * FIR_KG && !MISPEC_DBG(p, 0x1000)) {
+  if (stride == 2 && n_taps + 62 <= 8 * FIR_KG) {
     // dedicated kernel: span staged once in LDS, Toeplitz taps re-read from a tiny LDS table
     constexpr int NRW = FIR_NRW;
     constexpr int OUT_WG = 4096 * NRW;

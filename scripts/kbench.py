@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks on the GPU box: per-workload, per-tile timings of the C-ABI calls
 (events on the launch stream).  Usage: python scripts/kbench.py [stft|cqt|mel|cqt2010|fir|all]
-The rows that pass `_debug` bits (ablations, A/B kernel selectors) run on the benchmarking
+The rows that pass `_debug` bits (ablations) run on the benchmarking
 build of the library: python -m nnaudio_amd.build --ablate"""
 import os
 import sys
@@ -46,7 +46,7 @@ def stft():
     ms = timeit(lambda: engine.framed_gemm(x, m.wcos[:1024], m.wsin[:1024], hop=512, pad=1024, pad_mode=2,
                                            epilogue=engine.EPI_MAGNITUDE, tile=1))
     print("stft 1024 bins only (16 full row blocks, unmasked): %.3f ms -> %.1f TF" % (ms, 2.0*2048*2048*64*862/ms/1e9))
-    for dbg, what in ((0, "auto (LDS-direct)"), (0x800, "register-staged"), (0x100, "frame-tile-fastest order"), (0x200, "L2-blocked order"), (1, "no global loads"), (16, "no MFMA (load path only)"), (16 + 8, "no MFMA, no frag reads")):
+    for dbg, what in ((0, "full"), (1, "no global loads"), (16, "no MFMA (load path only)"), (16 + 8, "no MFMA, no frag reads")):
         ms = timeit(lambda: engine.framed_gemm(x, m.wcos[:1024], m.wsin[:1024], hop=512, pad=1024, pad_mode=2,
                                                epilogue=engine.EPI_MAGNITUDE, tile=1, _debug=dbg))
         print("ablate[%-28s] tile 1, 1024 bins: %.3f ms -> %.1f TF (%.1f%%)" % (what, ms, 2.0*2048*2048*64*862/ms/1e9, 2.0*2048*2048*64*862/ms/1e9/1.573))
@@ -64,12 +64,14 @@ def fold():
     prep = engine.prepare_basis(m.wcos, m.wsin, "bf16x3", hop=512)
     for dbg, what in ((0, "full step (pre-pass + contraction)"), (1, "no LDS-DMA in the loop"),
                       (8, "no fragment reads"), (1 + 8, "no DMA, no fragment reads (MFMA + barrier)"),
-                      (1 + 8 + 4, "MFMAs only"), (0x40000, "no epilogue"), (0x40000 + 1, "no epilogue, no DMA"),
-                      (0x100000, "dense (unfolded) kernel")):
+                      (1 + 8 + 4, "MFMAs only"), (0x40000, "no epilogue"), (0x40000 + 1, "no epilogue, no DMA")):
         ms = timeit(lambda: engine.framed_gemm(x, m.wcos, m.wsin, hop=512, pad=1024, pad_mode=2,
                                                epilogue=engine.EPI_MAGNITUDE, precision="bf16x3",
                                                _debug=dbg, **prep), n=30, w=10)
         print("fold[%-44s] %.3f ms" % (what, ms))
+    ms = timeit(lambda: engine.framed_gemm(x, m.wcos, m.wsin, hop=512, pad=1024, pad_mode=2, epilogue=engine.EPI_MAGNITUDE,
+                                           precision="bf16x3", basis_split=prep["basis_split"]), n=30, w=10)
+    print("fold[%-44s] %.3f ms" % ("dense (unfolded) kernel: no folded planes", ms))
 
 
 def pyramid():
