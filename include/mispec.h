@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MISPEC_ABI_VERSION 16
+#define MISPEC_ABI_VERSION 17
 
 enum {
   MISPEC_OK = 0,
@@ -558,6 +558,54 @@ typedef struct mispec_cfp_args {
 int mispec_cfp_f32(const mispec_cfp_args *args, void *stream);
 int mispec_cfp_served(int32_t n_fft, int32_t window_size, int32_t n_out, int32_t n_layers, int32_t log_layer);
 int mispec_cfp_twiddles_host(int32_t n_fft, float *dst);
+
+/*
+ * Mel spectrogram -> magnitude (power == 1) or power (power == 2) spectrogram: per frame column the non-negative least
+ * squares problem  min_{p >= 0} || M p - m ||^2  for the filterbank M (n_mels, n_bins), by a FIXED number of projected
+ * gradient steps (no early stopping, no host synchronisation):
+ *   p = y = 0;  n_iter times:  r = M y - m;  p+ = max(y - eta M^T r, 0);  y = p+ + beta[k] (p+ - p);  p = p+
+ *   out = p ** (1 / power)
+ * in ONE launch: a workgroup takes mispec_mel_nnls_tile_frames(n_bins) consecutive frames of a clip, keeps the bank as
+ * sparse tables and the tile in LDS and runs all steps (csrc/mel_nnls.hip, the tables and the arithmetic: csrc/mel_nnls.h).
+ * The iterate is kept in float64 and rounded to float32 once, at the store.
+ * eta = 1 / (largest eigenvalue of M M^T) and beta (n_iter floats, DEVICE; Nesterov's (t_k - 1) / t_{k+1} or zeros) are
+ * the caller's.  mel[c, r, t] at c mel_clip_stride + r mel_row_stride + t, out[c, b, t] likewise.
+ *
+ * mispec_mel_nnls_served: 1 when the kernel serves the bank (HOST pointer, rows row_stride floats apart), else 0: the
+ *   non-zeros of every row contiguous (rows without any are allowed), the starts and the stops of the rows with non-zeros
+ *   non-decreasing, at most 4 rows over a bin, n_mels <= 256, n_bins <= 2049 (n_fft <= 4096), power > 0.
+ * mispec_mel_nnls_tables_host: sizes[0 .. 3) = words of the tables, n_act (rows with non-zeros), nnz; dst (HOST pointer,
+ *   dst_words 32-bit words; NULL: sizes only) = the tables, which the caller copies to the device.  E_UNSUPPORTED for a
+ *   bank the query refuses.
+ */
+typedef struct mispec_mel_nnls_args {
+  uint32_t struct_size;      /* sizeof(mispec_mel_nnls_args)                             */
+  int32_t n_mels;
+  int32_t n_bins;            /* F = n_fft / 2 + 1                                        */
+  int32_t n_clips;
+  int32_t n_frames;
+  int32_t n_iter;            /* >= 0 (0: out = 0)                                        */
+  const float *mel;          /* (n_clips, n_mels, n_frames)                              */
+  int64_t mel_clip_stride;
+  int64_t mel_row_stride;
+  const int32_t *tables;     /* DEVICE copy of mispec_mel_nnls_tables_host's dst         */
+  int32_t table_words;       /* sizes[0]                                                 */
+  int32_t n_act;             /* sizes[1]                                                 */
+  int32_t nnz;               /* sizes[2]                                                 */
+  int32_t reserved;          /* 0                                                        */
+  const float *beta;         /* (n_iter), DEVICE                                         */
+  double eta;
+  float power;
+  int32_t reserved2;         /* 0                                                        */
+  float *out;                /* (n_clips, n_bins, n_frames)                              */
+  int64_t out_clip_stride;
+  int64_t out_row_stride;
+} mispec_mel_nnls_args;
+int mispec_mel_nnls_f32(const mispec_mel_nnls_args *args, void *stream);
+int mispec_mel_nnls_served(const float *basis_host, int64_t row_stride, int32_t n_mels, int32_t n_bins, float power);
+int mispec_mel_nnls_tables_host(const float *basis_host, int64_t row_stride, int32_t n_mels, int32_t n_bins, int32_t *dst,
+                                int64_t dst_words, int32_t *sizes);
+int32_t mispec_mel_nnls_tile_frames(int32_t n_bins);
 
 /*
  * power_to_db of MFCC (mel.py:263-279), per clip c over its `clip_elems` values (n_mels * n_frames):

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmispec.so")
 ABLATE_LIB_PATH = os.path.join(_HERE, "csrc", "libmispec_ablate.so")  # benchmarking build
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3
 
 # enums (mirror include/mispec.h)
@@ -80,6 +80,10 @@ EXPORTS = (
     "mispec_cfp_f32",
     "mispec_cfp_served",
     "mispec_cfp_twiddles_host",
+    "mispec_mel_nnls_f32",
+    "mispec_mel_nnls_served",
+    "mispec_mel_nnls_tables_host",
+    "mispec_mel_nnls_tile_frames",
 )
 
 
@@ -116,6 +120,34 @@ class CfpArgs(ctypes.Structure):
         ("l0", ctypes.c_void_p),
         ("lf", ctypes.c_void_p),
         ("lq", ctypes.c_void_p),
+        ("out_clip_stride", ctypes.c_int64),
+        ("out_row_stride", ctypes.c_int64),
+    ]
+
+
+class MelNnlsArgs(ctypes.Structure):
+    """struct mispec_mel_nnls_args"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("n_mels", ctypes.c_int32),
+        ("n_bins", ctypes.c_int32),
+        ("n_clips", ctypes.c_int32),
+        ("n_frames", ctypes.c_int32),
+        ("n_iter", ctypes.c_int32),
+        ("mel", ctypes.c_void_p),
+        ("mel_clip_stride", ctypes.c_int64),
+        ("mel_row_stride", ctypes.c_int64),
+        ("tables", ctypes.c_void_p),
+        ("table_words", ctypes.c_int32),
+        ("n_act", ctypes.c_int32),
+        ("nnz", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("beta", ctypes.c_void_p),
+        ("eta", ctypes.c_double),
+        ("power", ctypes.c_float),
+        ("reserved2", ctypes.c_int32),
+        ("out", ctypes.c_void_p),
         ("out_clip_stride", ctypes.c_int64),
         ("out_row_stride", ctypes.c_int64),
     ]
@@ -484,6 +516,15 @@ def _load(path, how):
     lib.mispec_cfp_served.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     lib.mispec_cfp_twiddles_host.restype = ctypes.c_int
     lib.mispec_cfp_twiddles_host.argtypes = [ctypes.c_int32, ctypes.c_void_p]
+    lib.mispec_mel_nnls_f32.restype = ctypes.c_int
+    lib.mispec_mel_nnls_f32.argtypes = [ctypes.POINTER(MelNnlsArgs), ctypes.c_void_p]
+    lib.mispec_mel_nnls_served.restype = ctypes.c_int
+    lib.mispec_mel_nnls_served.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float]
+    lib.mispec_mel_nnls_tables_host.restype = ctypes.c_int
+    lib.mispec_mel_nnls_tables_host.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    lib.mispec_mel_nnls_tile_frames.restype = ctypes.c_int32
+    lib.mispec_mel_nnls_tile_frames.argtypes = [ctypes.c_int32]
     lib.mispec_overlap_add_f32.restype = ctypes.c_int
     lib.mispec_overlap_add_f32.argtypes = [
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,

@@ -1909,3 +1909,165 @@ def cfp(x, h, fmat, qmat, *, N, hop, g, tc_idx, fc_idx, first_frame, n_frames, o
         _abi.check(_abi.load().mispec_cfp_f32(ctypes.byref(a), torch.cuda.current_stream(x.device).cuda_stream))
     _cfp_route.name = "kernel"
     return tuple(outs)
+
+
+# ---------------------------------------------------------------------------------------------- #
+# Mel inversion (features/mel.py: MelSpectrogram.to_stft / inverse): non-negative least squares per frame column
+# ---------------------------------------------------------------------------------------------- #
+_mel_nnls_kernel = os.environ.get("MISPEC_MEL_NNLS_KERNEL", "1") not in ("0", "false", "off")
+_mel_nnls_route = threading.local()
+
+
+def set_mel_nnls_kernel(enabled):
+    """Mel inversion on CUDA tensors: all projected-gradient steps of a tile of frames in one workgroup
+    (``mispec_mel_nnls_f32``) where the library serves the bank; ``False`` (or ``MISPEC_MEL_NNLS_KERNEL=0``) runs the
+    composition of torch operators (``mel_nnls_composition``) instead.  Returns the previous setting."""
+    global _mel_nnls_kernel
+    old, _mel_nnls_kernel = _mel_nnls_kernel, bool(enabled)
+    return old
+
+
+def mel_nnls_route():
+    """Which route the last ``mel_nnls`` call of this thread took: "kernel" or "composition" (None: no call yet)."""
+    return getattr(_mel_nnls_route, "name", None)
+
+
+def mel_nnls_served(basis, power):
+    """Whether ``mispec_mel_nnls_f32`` serves this filterbank (the library's rule: ``mispec_mel_nnls_served``, which
+    reads a host copy of the bank)."""
+    if basis.dim() != 2:
+        return False
+    b = np.ascontiguousarray(basis.detach().to(torch.float32).cpu().numpy())
+    return _abi.load().mispec_mel_nnls_served(b.ctypes.data, b.shape[1], b.shape[0], b.shape[1], float(power)) == 1
+
+
+def mel_nnls_betas(n_iter, momentum):
+    """The momentum table: beta_k = (t_k - 1) / t_{k+1}, t_0 = 1, t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2, evaluated in
+    float64 and rounded to float32 (every route reads this table); all zeros without momentum."""
+    beta = np.zeros(int(n_iter), dtype=np.float32)
+    if momentum:
+        t = 1.0
+        for k in range(int(n_iter)):
+            t_next = (1.0 + np.sqrt(1.0 + 4.0 * t * t)) / 2.0
+            beta[k] = (t - 1.0) / t_next
+            t = t_next
+    return beta
+
+
+def mel_nnls_operands(basis, power):
+    """What the inversion needs besides the bank, on its device: ``L`` (largest eigenvalue of M M^T, float64 on the
+    host), whether the kernel serves the bank and, if so, its sparse tables (built by the library) with their sizes;
+    ``betas``: a per-(n_iter, momentum) cache of the momentum tables, host and device."""
+    m = np.ascontiguousarray(basis.detach().to(torch.float32).cpu().numpy())
+    m64 = m.astype(np.float64)
+    L = float(np.linalg.eigvalsh(m64 @ m64.T)[-1]) if m.size else 0.0
+    ops = {"L": max(L, 0.0), "served": False, "tables": None, "sizes": None, "betas": {}, "device": basis.device}
+    lib = _abi.load()
+    if lib.mispec_mel_nnls_served(m.ctypes.data, m.shape[1], m.shape[0], m.shape[1], float(power)) == 1:
+        sizes = np.zeros(3, dtype=np.int32)
+        _abi.check(lib.mispec_mel_nnls_tables_host(m.ctypes.data, m.shape[1], m.shape[0], m.shape[1], None, 0, sizes.ctypes.data))
+        blob = np.zeros(int(sizes[0]), dtype=np.int32)
+        _abi.check(lib.mispec_mel_nnls_tables_host(m.ctypes.data, m.shape[1], m.shape[0], m.shape[1], blob.ctypes.data,
+                                                   blob.size, sizes.ctypes.data))
+        ops["served"], ops["sizes"] = True, tuple(int(v) for v in sizes)
+        if basis.is_cuda:
+            ops["tables"] = torch.from_numpy(blob).to(basis.device)
+    return ops
+
+
+def _mel_nnls_betas_of(ops, n_iter, momentum, device):
+    key = (int(n_iter), bool(momentum))
+    hit = ops["betas"].get(key)
+    if hit is None:
+        host = mel_nnls_betas(n_iter, momentum)
+        hit = (host, torch.from_numpy(host).to(device) if device.type == "cuda" else None)
+        ops["betas"] = {key: hit}  # (one entry: the settings of a module rarely change)
+    return hit
+
+
+def mel_nnls_composition(mel, basis, *, power, n_iter, momentum, L=None, betas=None, dtype=torch.float64):
+    """The inversion as torch operators on ``mel``'s device (two dense matmuls and the elementwise steps per
+    iteration): what CPU tensors, banks the kernel does not serve (dense, trained, gammatone-like) and ``torch.compile``
+    run.  The iterate is kept in ``dtype`` and rounded to float32 once, at the end: float64 by default, as in the
+    kernel (a float32 iterate leaves the rounding of the loud bins in the quiet ones beside them: csrc/mel_nnls.h);
+    ``dtype=torch.float32`` is the operator sequence the kernel is timed against (scripts/mel_inverse_time.py).
+    ``L`` / ``betas``: the cached operands, else derived."""
+    M = basis.detach().to(device=mel.device, dtype=dtype)
+    if L is None:
+        m64 = basis.detach().double().cpu().numpy()
+        L = float(np.linalg.eigvalsh(m64 @ m64.T)[-1]) if m64.size else 0.0
+    if betas is None:
+        betas = mel_nnls_betas(n_iter, momentum)
+    B, _, T = mel.shape
+    p = torch.zeros((B, M.shape[1], T), dtype=dtype, device=mel.device)
+    if L <= 0.0 or n_iter <= 0:
+        return p.to(torch.float32)
+    eta = 1.0 / L if dtype == torch.float64 else float(np.float32(1.0 / L))
+    Mt = M.t().contiguous()
+    m = mel.to(dtype)
+    y = p
+    for k in range(int(n_iter)):
+        r = torch.matmul(M, y) - m
+        pn = torch.clamp_min(y - eta * torch.matmul(Mt, r), 0.0)
+        y = pn + float(betas[k]) * (pn - p)
+        p = pn
+    if power != 1:
+        p = torch.sqrt(p) if power == 2 else p.pow(1.0 / float(power))
+    return p.to(torch.float32)
+
+
+def mel_nnls(mel, basis, *, power, n_iter, momentum, operands=None, out=None):
+    """Non-negative spectrum ``(B, F, T)`` whose projection through ``basis`` (n_mels, F) matches the float32 ``mel``
+    ``(B, n_mels, T)`` (the algorithm: ``MelSpectrogram.to_stft``).  CUDA tensors with a bank the library serves
+    (``mel_nnls_served``) take the kernel, everything else ``mel_nnls_composition``; ``mel_nnls_route()`` tells which.
+    ``operands``: a callable returning ``mel_nnls_operands(...)`` (the module's cache).  ``out``: a float32 ``(B, F, T)``
+    tensor on ``mel``'s device to write into (frames of unit stride; it may be a view of a wider allocation)."""
+    if not power > 0:
+        raise ValueError("mel_nnls: power must be positive, got %r" % (power,))
+    n_iter = int(n_iter)
+    if n_iter < 0:
+        raise ValueError("mel_nnls: n_iter must be >= 0")
+    B, n_mels, T = mel.shape
+    F = basis.shape[1]
+    if out is not None:
+        if (tuple(out.shape) != (B, F, T) or out.dtype != torch.float32 or out.device != mel.device or
+                (T > 1 and out.stride(2) != 1) or out.stride(1) < T or out.stride(0) < F * out.stride(1)):
+            raise ValueError("mel_nnls: out must be a float32 (%d, %d, %d) tensor on %s with frames of unit stride"
+                             % (B, F, T, mel.device))
+
+    def deliver(res):
+        if out is None:
+            return res
+        out.copy_(res)
+        return out
+
+    if B == 0 or T == 0:
+        _mel_nnls_route.name = "composition"
+        return deliver(torch.zeros((B, F, T), dtype=torch.float32, device=mel.device))
+    if compiling():
+        _mel_nnls_route.name = "composition"
+        return deliver(mel_nnls_composition(mel, basis, power=power, n_iter=n_iter, momentum=momentum))
+    ops = operands() if operands is not None else mel_nnls_operands(basis, power)
+    host_betas, dev_betas = _mel_nnls_betas_of(ops, n_iter, momentum, mel.device)
+    use_kernel = mel.is_cuda and _mel_nnls_kernel and ops["served"] and ops["tables"] is not None and B <= 65535
+    if not use_kernel or ops["L"] <= 0.0:
+        _mel_nnls_route.name = "composition"
+        return deliver(mel_nnls_composition(mel, basis, power=power, n_iter=n_iter, momentum=momentum, L=ops["L"],
+                                            betas=host_betas))
+    if mel.stride(2) != 1 or mel.stride(1) < T or mel.stride(0) < n_mels * mel.stride(1):
+        mel = mel.contiguous()  # (rows of unit stride, no overlap: what the library takes)
+    if out is None:
+        out = torch.empty((B, F, T), dtype=torch.float32, device=mel.device)
+    a = _abi.MelNnlsArgs()
+    a.struct_size = ctypes.sizeof(_abi.MelNnlsArgs)
+    a.n_mels, a.n_bins, a.n_clips, a.n_frames, a.n_iter = n_mels, F, B, T, n_iter
+    a.mel, a.mel_clip_stride, a.mel_row_stride = mel.data_ptr(), mel.stride(0), mel.stride(1)
+    a.tables = ops["tables"].data_ptr()
+    a.table_words, a.n_act, a.nnz = ops["sizes"]
+    a.beta = dev_betas.data_ptr() if n_iter > 0 else None
+    a.eta, a.power = 1.0 / ops["L"], float(power)
+    a.out, a.out_clip_stride, a.out_row_stride = out.data_ptr(), out.stride(0), out.stride(1)
+    with torch.cuda.device(mel.device):
+        _abi.check(_abi.load().mispec_mel_nnls_f32(ctypes.byref(a), torch.cuda.current_stream(mel.device).cuda_stream))
+    _mel_nnls_route.name = "kernel"
+    return out
