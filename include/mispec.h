@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MISPEC_ABI_VERSION 17
+#define MISPEC_ABI_VERSION 18
 
 enum {
   MISPEC_OK = 0,
@@ -606,6 +606,59 @@ int mispec_mel_nnls_served(const float *basis_host, int64_t row_stride, int32_t 
 int mispec_mel_nnls_tables_host(const float *basis_host, int64_t row_stride, int32_t n_mels, int32_t n_bins, int32_t *dst,
                                 int64_t dst_words, int32_t *sizes);
 int32_t mispec_mel_nnls_tile_frames(int32_t n_bins);
+
+/*
+ * Per-channel energy normalisation (Wang et al. 2017; librosa.pcen with max_size = 1) of a non-negative spectrogram
+ * s (n_clips, n_rows, n_frames), time last, per row (clip c, channel r):
+ *   M[-1] = state_in[c, r] (NULL: s[c, r, 0]);   M[t] = (1 - b) M[t-1] + b s[t]
+ *   out[t] = (s[t] (eps + M[t])^(-gain) + bias)^power - bias^power
+ * b, gain, bias, power: n_params floats each, n_params = 1 (one value for all channels) or n_rows (one per channel).
+ * One wave per row solves the recurrence by a scan over chunks of 64 frames (csrc/pcen.hip, the arithmetic:
+ * csrc/pcen.h).  s[c, r, t] at c s_clip_stride + r s_row_stride + t, out / grad_out / grad_s likewise; m_out, m,
+ * state_in, state_out, grad_state and sums are contiguous.
+ *
+ * mispec_pcen_f32: out, and where the pointers are not NULL m_out (n_clips, n_rows, n_frames) = M in float64 and state_out
+ *   (n_clips, n_rows) = M[n_frames - 1].  The backward's fields are not read.
+ * mispec_pcen_host_f32: the same on HOST pointers, the calling thread running the kernel's chunked arithmetic.
+ * mispec_pcen_bwd_f32: from s, m (the forward's m_out) and grad_out: grad_s, grad_state (with state_in; without one the
+ *   gradient through M[-1] = s[0] is added to grad_s[.., 0]) and sums (n_clips n_rows, 4) float64, 32-byte aligned: per
+ *   row the sums over t of the gradients of b, gain, bias, power, which the caller adds over the clips (and over the
+ *   channels when n_params = 1).  No atomics: the result is deterministic.  out, m_out, state_out are not read.
+ */
+typedef struct mispec_pcen_args {
+  uint32_t struct_size;      /* sizeof(mispec_pcen_args)                                  */
+  int32_t n_clips;
+  int32_t n_rows;            /* channels F                                               */
+  int32_t n_frames;
+  int32_t n_params;          /* 1 or n_rows                                              */
+  float eps;                 /* > 0                                                      */
+  const float *s;
+  int64_t s_clip_stride;
+  int64_t s_row_stride;
+  const float *b;            /* (n_params) each                                          */
+  const float *gain;
+  const float *bias;
+  const float *power;
+  const float *state_in;     /* (n_clips, n_rows) or NULL                                */
+  float *out;
+  int64_t out_clip_stride;
+  int64_t out_row_stride;
+  double *m_out;             /* (n_clips, n_rows, n_frames) float64, or NULL             */
+  float *state_out;          /* (n_clips, n_rows) or NULL                                */
+  const double *m;           /* backward: the forward's m_out                            */
+  const float *grad_out;
+  int64_t grad_out_clip_stride;
+  int64_t grad_out_row_stride;
+  float *grad_s;
+  int64_t grad_s_clip_stride;
+  int64_t grad_s_row_stride;
+  float *grad_state;         /* (n_clips, n_rows); NULL exactly when state_in is         */
+  double *sums;              /* (n_clips n_rows, 4)                                      */
+  int64_t reserved;          /* 0                                                        */
+} mispec_pcen_args;
+int mispec_pcen_f32(const mispec_pcen_args *args, void *stream);
+int mispec_pcen_bwd_f32(const mispec_pcen_args *args, void *stream);
+int mispec_pcen_host_f32(const mispec_pcen_args *args);
 
 /*
  * power_to_db of MFCC (mel.py:263-279), per clip c over its `clip_elems` values (n_mels * n_frames):

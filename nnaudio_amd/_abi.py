@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmispec.so")
 ABLATE_LIB_PATH = os.path.join(_HERE, "csrc", "libmispec_ablate.so")  # benchmarking build
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 E_INVALID, E_UNSUPPORTED, E_HIP = -1, -2, -3
 
 # enums (mirror include/mispec.h)
@@ -84,6 +84,9 @@ EXPORTS = (
     "mispec_mel_nnls_served",
     "mispec_mel_nnls_tables_host",
     "mispec_mel_nnls_tile_frames",
+    "mispec_pcen_f32",
+    "mispec_pcen_bwd_f32",
+    "mispec_pcen_host_f32",
 )
 
 
@@ -150,6 +153,42 @@ class MelNnlsArgs(ctypes.Structure):
         ("out", ctypes.c_void_p),
         ("out_clip_stride", ctypes.c_int64),
         ("out_row_stride", ctypes.c_int64),
+    ]
+
+
+class PcenArgs(ctypes.Structure):
+    """struct mispec_pcen_args"""
+
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("n_clips", ctypes.c_int32),
+        ("n_rows", ctypes.c_int32),
+        ("n_frames", ctypes.c_int32),
+        ("n_params", ctypes.c_int32),
+        ("eps", ctypes.c_float),
+        ("s", ctypes.c_void_p),
+        ("s_clip_stride", ctypes.c_int64),
+        ("s_row_stride", ctypes.c_int64),
+        ("b", ctypes.c_void_p),
+        ("gain", ctypes.c_void_p),
+        ("bias", ctypes.c_void_p),
+        ("power", ctypes.c_void_p),
+        ("state_in", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("out_clip_stride", ctypes.c_int64),
+        ("out_row_stride", ctypes.c_int64),
+        ("m_out", ctypes.c_void_p),
+        ("state_out", ctypes.c_void_p),
+        ("m", ctypes.c_void_p),
+        ("grad_out", ctypes.c_void_p),
+        ("grad_out_clip_stride", ctypes.c_int64),
+        ("grad_out_row_stride", ctypes.c_int64),
+        ("grad_s", ctypes.c_void_p),
+        ("grad_s_clip_stride", ctypes.c_int64),
+        ("grad_s_row_stride", ctypes.c_int64),
+        ("grad_state", ctypes.c_void_p),
+        ("sums", ctypes.c_void_p),
+        ("reserved", ctypes.c_int64),
     ]
 
 
@@ -525,6 +564,12 @@ def _load(path, how):
                                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     lib.mispec_mel_nnls_tile_frames.restype = ctypes.c_int32
     lib.mispec_mel_nnls_tile_frames.argtypes = [ctypes.c_int32]
+    lib.mispec_pcen_f32.restype = ctypes.c_int
+    lib.mispec_pcen_f32.argtypes = [ctypes.POINTER(PcenArgs), ctypes.c_void_p]
+    lib.mispec_pcen_bwd_f32.restype = ctypes.c_int
+    lib.mispec_pcen_bwd_f32.argtypes = [ctypes.POINTER(PcenArgs), ctypes.c_void_p]
+    lib.mispec_pcen_host_f32.restype = ctypes.c_int
+    lib.mispec_pcen_host_f32.argtypes = [ctypes.POINTER(PcenArgs)]
     lib.mispec_overlap_add_f32.restype = ctypes.c_int
     lib.mispec_overlap_add_f32.argtypes = [
         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,

@@ -23,7 +23,8 @@ def hipcc():
 
 # translation units of the library: (source, takes -DMISPEC_ABLATE in the benchmarking build)
 UNITS = [(SRC, True), (os.path.join(HERE, "csrc", "octave_stream.hip"), True), (os.path.join(HERE, "csrc", "cqt_chain.hip"), False),
-         (os.path.join(HERE, "csrc", "cfp.hip"), False), (os.path.join(HERE, "csrc", "mel_nnls.hip"), False)]
+         (os.path.join(HERE, "csrc", "cfp.hip"), False), (os.path.join(HERE, "csrc", "mel_nnls.hip"), False),
+         (os.path.join(HERE, "csrc", "pcen.hip"), False)]
 # the units that include fft_core.h (directly or through cfp_fft.h)
 FFT_CORE_UNITS = (SRC, os.path.join(HERE, "csrc", "cfp.hip"))
 
@@ -113,10 +114,10 @@ def _compile(src, obj, ablate, verbose):
         if os.path.exists(tmp):
             os.remove(tmp)
         raise subprocess.CalledProcessError(res.returncode, cmd)
-    if any(v > 0 and k.startswith(("octave_stream", "cqt_chain", "cfp_", "mel_nnls_")) for k, v in remarks.items()):
+    if any(v > 0 and k.startswith(("octave_stream", "cqt_chain", "cfp_", "mel_nnls_", "pcen_")) for k, v in remarks.items()):
         traffic = scratch_instructions(tmp)
         for k in list(remarks):
-            if k.startswith(("octave_stream", "cqt_chain", "cfp_", "mel_nnls_")) and remarks[k] > 0 and traffic.get(k, 1) == 0:
+            if k.startswith(("octave_stream", "cqt_chain", "cfp_", "mel_nnls_", "pcen_")) and remarks[k] > 0 and traffic.get(k, 1) == 0:
                 remarks[k] = 0  # (a stack slot nobody loads or stores: SGPR spills in VGPR lanes)
     with open(_sidecar(obj) + ".tmp", "w") as f:
         json.dump({"flags": _flags_key(ablate), "scratch": remarks}, f)
@@ -132,6 +133,8 @@ def _compile(src, obj, ablate, verbose):
 #     lane, seen when the register slots were sized differently) runs every FFT pass through memory.  Refused outright.
 #   mel_nnls_*: p and y of a thread's bins must stay in registers over all iterations (that is the kernel's point): a build
 #     that indexes them through scratch reads and writes them in memory every step.  Refused outright.
+#   pcen_*: a wave's chunk, its scan factors and the float64 sums are a few dozen registers; scratch there means the
+#     factor table is indexed through memory on every shuffle step.  Refused outright.
 #   stft_fft_* / istft_*: their waits are "at most n operations outstanding, n = the stores issued after the loads": extra
 #     scratch operations behind the loads only make that wait stronger (in-order retirement, probed:
 #     experiments/ldsdma_hazard), so scratch there is slow, not wrong -- but it must not appear unnoticed: refused unless
@@ -153,7 +156,7 @@ def refused_scratch(remarks, ablate):
     for k, v in remarks.items():
         if v <= 0:
             continue
-        if k.startswith(("framed_", "octave_stream", "cqt_chain", "cfp_", "mel_nnls_")):
+        if k.startswith(("framed_", "octave_stream", "cqt_chain", "cfp_", "mel_nnls_", "pcen_")):
             if ablate and k.startswith("octave_stream"):
                 continue  # (the benchmarking build's extra switches cost the streaming octave kernel a few registers)
             bad[k] = v
@@ -195,6 +198,8 @@ def build(force=False, verbose=True, ablate=False):
                 mine = [d for d in mine if not d.endswith("cfp_fft.h")]
             if os.path.basename(src) != "mel_nnls.hip":
                 mine = [d for d in mine if not d.endswith("mel_nnls.h")]
+            if os.path.basename(src) != "pcen.hip":
+                mine = [d for d in mine if not d.endswith("pcen.h")]
             cached = None if force else _cached_remarks(obj, ablate and takes_ablate)
             if cached is None or os.path.getmtime(obj) < max(os.path.getmtime(d) for d in mine):
                 jobs.append((obj, ex.submit(_compile, src, obj, ablate and takes_ablate, verbose)))

@@ -2071,3 +2071,174 @@ def mel_nnls(mel, basis, *, power, n_iter, momentum, operands=None, out=None):
         _abi.check(_abi.load().mispec_mel_nnls_f32(ctypes.byref(a), torch.cuda.current_stream(mel.device).cuda_stream))
     _mel_nnls_route.name = "kernel"
     return out
+
+
+# ---------------------------------------------------------------------------------------------- #
+# PCEN (features/pcen.py): per-channel energy normalisation, a first-order recurrence along time
+# ---------------------------------------------------------------------------------------------- #
+_pcen_kernel = os.environ.get("MISPEC_PCEN_KERNEL", "1") not in ("0", "false", "off")
+_pcen_route = threading.local()
+
+
+def set_pcen_kernel(enabled):
+    """PCEN on CUDA tensors: one wave per row scans the smoother's recurrence (``mispec_pcen_f32`` and, in grad mode,
+    ``mispec_pcen_bwd_f32``); ``False`` (or ``MISPEC_PCEN_KERNEL=0``) runs the composition of torch operators
+    (``pcen_composition``) instead.  Returns the previous setting."""
+    global _pcen_kernel
+    old, _pcen_kernel = _pcen_kernel, bool(enabled)
+    return old
+
+
+def pcen_route():
+    """Which route the last ``pcen`` call of this thread took: "kernel", "host" or "composition" (None: no call yet)."""
+    return getattr(_pcen_route, "name", None)
+
+
+def pcen_composition(S, b, gain, bias, power, eps, state=None, dtype=torch.float64):
+    """PCEN as torch operators on ``S``'s device: the smoother as a loop over the frames, then the pointwise part.
+    ``S`` (B, F, T); the parameters ``(1,)`` or ``(F,)``; ``state`` (B, F) or None (then ``S[..., 0]``).  Everything is
+    evaluated in ``dtype`` and rounded to ``S``'s type once, at the end: float64 by default, as in the kernel (with
+    float32 steps a row of one or two frames misses the suite's rule now and then: csrc/pcen.h); ``dtype=torch.float32``
+    is the operator sequence the kernel is timed against and the yardstick of its gradients.  Differentiable by
+    autograd -- on float64 input it is the truth the kernels' gradients are tested against.  Returns ``(out, M[..., -1])``."""
+    def col(p):
+        return p.to(device=S.device, dtype=dtype).reshape(1, -1)
+
+    b, gain, bias, power = col(b), col(gain), col(bias), col(power)
+    x = S.to(dtype)
+    m = x[..., 0] if state is None else state.to(device=S.device, dtype=dtype)
+    steps = []
+    for t in range(x.shape[-1]):
+        m = (1.0 - b) * m + b * x[..., t]
+        steps.append(m)
+    M = torch.stack(steps, dim=-1)
+    g3, s3, p3 = gain[..., None], bias[..., None], power[..., None]
+    # (bias ** power on a tensor of the output's shape: the same elementwise kernel at the same positions as the first
+    # power, so that an all-zero input gives exactly zero)
+    out = (x * (eps + M) ** (-g3) + s3) ** p3 - (torch.zeros_like(x) + s3) ** p3
+    return out.to(S.dtype), m.to(S.dtype)
+
+
+def _pcen_strides(t):
+    """(clip, row) strides to state for a (B, F, T) tensor ``_pcen_rows`` passed: the stride of a dimension of size 1
+    addresses nothing and may hold anything, so the contiguous value stands in for it."""
+    B, F, T = t.shape
+    row = t.stride(1) if F > 1 else T
+    return (t.stride(0) if B > 1 else F * row), row
+
+
+def _pcen_rows(t):
+    """``t`` with frames of unit stride and rows that do not overlap (what the library takes), made contiguous when it
+    is not; clip and row strides pass through."""
+    B, F, T = t.shape
+    if (T > 1 and t.stride(2) != 1) or (F > 1 and t.stride(1) < T):
+        return t.contiguous()
+    if B > 1 and t.stride(0) < F * _pcen_strides(t)[1]:
+        return t.contiguous()
+    return t
+
+
+def _pcen_args(S, params, eps, state):
+    B, F, T = S.shape
+    a = _abi.PcenArgs()
+    a.struct_size = ctypes.sizeof(_abi.PcenArgs)
+    a.n_clips, a.n_rows, a.n_frames, a.n_params, a.eps = B, F, T, params[0].numel(), float(eps)
+    a.s = S.data_ptr()
+    a.s_clip_stride, a.s_row_stride = _pcen_strides(S)
+    a.b, a.gain, a.bias, a.power = (p.data_ptr() for p in params)
+    a.state_in = None if state is None else state.data_ptr()
+    return a
+
+
+def _pcen_forward(S, params, eps, state, want_m):
+    """The library's forward on ``S``'s device: (out, M or None, last state)."""
+    B, F, T = S.shape
+    dev = S.device
+    out = alloc_out((B, F, T), dev)
+    m = torch.empty((B, F, T), dtype=torch.float64, device=dev) if want_m else None
+    last = torch.empty((B, F), dtype=torch.float32, device=dev)
+    a = _pcen_args(S, params, eps, state)
+    a.out, a.out_clip_stride, a.out_row_stride = out.data_ptr(), F * T, T
+    a.m_out = None if m is None else m.data_ptr()
+    a.state_out = last.data_ptr()
+    lib = _abi.load()
+    if dev.type == "cpu":
+        _abi.check(lib.mispec_pcen_host_f32(ctypes.byref(a)))
+    else:
+        with torch.cuda.device(dev):
+            _abi.check(lib.mispec_pcen_f32(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream))
+    return out, m, last
+
+
+class _PcenFn(torch.autograd.Function):
+    """inputs: S (B, F, T), state (B, F) or None, the four parameters; outputs: out and the (non-differentiable) last state"""
+
+    @staticmethod
+    def forward(ctx, S, state, b, gain, bias, power, eps):
+        Sd = _pcen_rows(S.detach())
+        params = tuple(p.detach().contiguous() for p in (b, gain, bias, power))
+        st = None if state is None else state.detach().contiguous()
+        out, m, last = _pcen_forward(Sd, params, eps, st, True)
+        ctx.save_for_backward(Sd, m, *params, *(() if st is None else (st,)))
+        ctx.eps = float(eps)
+        ctx.mark_non_differentiable(last)
+        return out, last
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_last):
+        Sd, m, *params = ctx.saved_tensors[:6]
+        st = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        B, F, T = Sd.shape
+        dev = Sd.device
+        go = _pcen_rows(_f32(grad_out, "grad_output"))
+        dS = torch.empty((B, F, T), dtype=torch.float32, device=dev)
+        dstate = None if st is None else torch.empty((B, F), dtype=torch.float32, device=dev)
+        sums = torch.empty((B, F, 4), dtype=torch.float64, device=dev)
+        a = _pcen_args(Sd, params, ctx.eps, st)
+        a.m = m.data_ptr()
+        a.grad_out = go.data_ptr()
+        a.grad_out_clip_stride, a.grad_out_row_stride = _pcen_strides(go)
+        a.grad_s, a.grad_s_clip_stride, a.grad_s_row_stride = dS.data_ptr(), F * T, T
+        a.grad_state = None if dstate is None else dstate.data_ptr()
+        a.sums = sums.data_ptr()
+        with torch.cuda.device(dev):
+            _abi.check(_abi.load().mispec_pcen_bwd_f32(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream))
+        per = sums.sum(0)  # (F, 4), float64
+        if params[0].numel() == 1:
+            per = per.sum(0, keepdim=True)
+        grads = [per[:, j].to(torch.float32).reshape(params[j].shape) if ctx.needs_input_grad[2 + j] else None
+                 for j in range(4)]
+        return (dS if ctx.needs_input_grad[0] else None, dstate if ctx.needs_input_grad[1] else None, *grads, None)
+
+
+def pcen(S, b, gain, bias, power, eps, state=None):
+    """PCEN of the float32 ``S`` (B, F, T) -> ``(out, last state (B, F), detached)``.  CUDA tensors run the kernel (with
+    its backward kernel when ``S``, ``state`` or a parameter requires grad); CPU tensors without grad the library's
+    host loop; ``torch.compile``, CPU tensors with grad and ``set_pcen_kernel(False)`` the composition of torch
+    operators.  ``pcen_route()`` tells which."""
+    eps = float(np.float32(eps))  # (one float32 number on every route: the library's argument is a float)
+    tensors = (S, b, gain, bias, power) + (() if state is None else (state,))
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+    if S.shape[0] == 0 or S.shape[1] == 0 or S.shape[2] == 0:
+        raise ValueError("pcen: empty input of shape %s" % (tuple(S.shape),))
+    if compiling() or not _pcen_kernel or (not S.is_cuda and needs_grad):
+        _pcen_route.name = "composition"
+        out, last = pcen_composition(S, b, gain, bias, power, eps, state)
+        return out, last.detach()
+    if not S.is_cuda and not _host_path:
+        raise _gpu_only(S)
+    _f32(S, "spectrogram")
+    params = tuple(_f32(p, "parameter").to(S.device) for p in (b, gain, bias, power))
+    if params[0].numel() not in (1, S.shape[1]) or any(p.numel() != params[0].numel() for p in params):
+        raise ValueError("pcen: the parameters hold 1 or %d values each, got %s" % (S.shape[1], [p.numel() for p in params]))
+    if state is not None and tuple(state.shape) != tuple(S.shape[:2]):
+        raise ValueError("pcen: state must be %s, got %s" % (tuple(S.shape[:2]), tuple(state.shape)))
+    if state is not None:
+        state = _f32(state, "state").to(S.device)
+    _pcen_route.name = "kernel" if S.is_cuda else "host"
+    if needs_grad:
+        out, last = _PcenFn.apply(S, state, *params, float(eps))
+        return out, last
+    out, _, last = _pcen_forward(_pcen_rows(S.detach()), tuple(p.detach().contiguous() for p in params), eps,
+                                 None if state is None else state.detach().contiguous(), False)
+    return out, last
